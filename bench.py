@@ -17,6 +17,12 @@ itself (torch.distributed.run as a child process, before anything touches a GPU)
 status.  Every rank's context joins one RCCL communicator inside the C ABI (prt_shard_init_rccl): each renders
 its 32x32 pixel tiles (round-robin) and prt_render gathers the tile buffers on rank 0 with one ncclGather per
 frame; value = all ranks' rays / max-over-ranks time.
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds what the headline does
+not need: the roofline block of the traversal kernel (committed profiles priced against the timed library's code
+hash) and the CPU baseline legs.  The accumulation is reset after the warmup and the timed steps' frame indices do
+not depend on how many warmup frames ran, so the same arguments render the same images in every run;
+--dump-outputs DIR writes the last timed step's outputs (avg.npy, rgb8.npy) for comparing two builds.
 """
 import argparse
 import json
@@ -189,6 +195,25 @@ def default_inflight(gpus):
     return 4 if gpus >= 2 else 2
 
 
+DUMP_MAX_BYTES = 64_000_000  # --dump-outputs writes at most this much: a whole frame costs 16 B (avg) + 4 B (rgb8)
+DUMP_SAMPLE_PIXELS = 2_000_000  # per pixel; a sampled one 8 B more (its index): 56 MB
+
+
+def dump_outputs(outdir, avg, rgb8):
+    """--dump-outputs: what the last timed step returned, as float32 .npy files: avg.npy (pixels x 4, the running
+    average) and rgb8.npy (the 0x00RRGGBB screen pixels as numbers; 24 bits are exact in float32).  A frame above
+    DUMP_MAX_BYTES (1080p is 41 MB; 4K is not) is written as a fixed, seeded sample of DUMP_SAMPLE_PIXELS pixels,
+    whose row-major indices go to pixel_index.npy (float64)."""
+    os.makedirs(outdir, exist_ok=True)
+    n = avg.shape[0]
+    if n * 20 > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE_PIXELS, replace=False))
+        avg, rgb8 = avg[idx], rgb8[idx]
+        np.save(os.path.join(outdir, "pixel_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(outdir, "avg.npy"), np.ascontiguousarray(avg, dtype=np.float32))
+    np.save(os.path.join(outdir, "rgb8.npy"), (rgb8.astype(np.uint32) & np.uint32(0xFFFFFF)).astype(np.float32))
+
+
 def spawn_ranks(n):
     """--gpus N without WORLD_SIZE: start N ranks of this script under torch.distributed.run (a child process;
     nothing here has touched a GPU) and return their exit status."""
@@ -215,7 +240,13 @@ def main():
     ap.add_argument("--context-stream", default="own", choices=["own", "side"],
                     help="the context's HIP stream: its own (default; torch's null stream maps to it) or a torch side "
                          "stream (A/B, profiles/r06_stream_ab.txt)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also report what the headline does not need: the traversal kernel's roofline block and, "
+                         "on one GPU, the CPU baseline legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs to DIR/avg.npy and DIR/rgb8.npy "
+                         "(float32; a seeded sample of 2M pixels where the whole frame exceeds 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline legs")
     ap.add_argument("--inflight", type=int, default=None, choices=range(1, 9),
                     help="frames in flight (prt_set_frames_in_flight; default 2 on one GPU, 4 on several): "
                          "consecutive frames' wavefront chains overlap on internal streams; accumulation and "
@@ -321,6 +352,9 @@ def main():
         step(i, False)
     warm_steps = n0 + extra
     ctx.ray_totals(reset=True)  # waits for the warmup frames
+    # the warmup's length depends on the clock: the timed steps start from an empty accumulation at frame index
+    # fpc * n0 whatever it was, so their images are the same in every run with these arguments
+    ctx.reset_accumulation(full=True)
     if dist:
         dist.barrier()
     torch.cuda.synchronize()
@@ -329,7 +363,7 @@ def main():
     # event timers of the traversal kernel (stats=True; its host wait coincides with the closing synchronize).
     t0 = time.perf_counter()
     for i in range(args.steps):
-        st = step(warm_steps + i, i == args.steps - 1)
+        st = step(n0 + i, i == args.steps - 1)
     torch.cuda.synchronize()
     if dist:
         dist.barrier()
@@ -346,10 +380,16 @@ def main():
         dist.all_reduce(r)
         seg, shadow = int(r[0].item()), int(r[1].item())
     rays = seg + shadow
+    ms_step = elapsed * 1000.0 / args.steps
+    value = rays / elapsed / 1e6
+    if rank == 0 and args.dump_outputs:  # (rank 0's buffers hold the whole frame)
+        if args.host_out:
+            dump_outputs(args.dump_outputs, avg_h, rgb_h)
+        else:
+            dump_outputs(args.dump_outputs, avg.cpu().numpy(), rgb.cpu().numpy())
 
-    if rank == 0:
-        ms_step = elapsed * 1000.0 / args.steps
-        value = rays / elapsed / 1e6
+    roof = None
+    if rank == 0 and args.full:
         # Roofline of the dominant kernel (k_trace2: the merged closest + shadow traversal, one launch per
         # wavefront iteration), per launch.  Launch time: HIP events recorded on the render stream around every
         # launch of the last timed frame (stats.ms_closest sums them).  Counts per launch: rocprofv3 PMC passes of this same
@@ -435,6 +475,7 @@ def main():
                      "fractions (scripts/gpu_mem.sh TA / TD / TCP / TCC passes)",
             "bytes_per_ray": {k: round(v, 1) for k, v in bpr.items()},
         })
+    if rank == 0:
         out = {
             "metric": f"Mrays/s (closest-hit segments + shadow any-hit rays) at {W}x{H}, {args.spp} spp, depth {args.bounces}",
             "value": round(value, 2),
@@ -464,9 +505,10 @@ def main():
                        # reference's own "Mrays/s" label, pixels per second (Core/Renderer.cpp:473)
                        "mpaths_per_s": round(W * H * args.spp / (ms_step / 1e3) / 1e6, 2),
                        "reference_style_mrays_per_s": round(W * H / (ms_step / 1e3) / 1e6, 2)},
-            "roofline": roof,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            out["roofline"] = roof
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(sd, W, H, args.spp, args.bounces)
         print(json.dumps(out), flush=True)
     ctx.close()

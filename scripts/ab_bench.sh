@@ -19,7 +19,7 @@ for r in $(seq 1 "$R"); do
     [ "$envs" = "-" ] && envs=""
     case "$envs" in -*) echo "bad variant '$v': assignments only (VAR=value ...), or '-'"; exit 2 ;; esac
     log=gpurun_out/ab_${T}_${r}_${i}.log
-    env $envs timeout -k 10 300 python3 bench.py --no-cpu-baseline $args > "$log" 2>&1
+    env $envs timeout -k 10 300 python3 bench.py --full --no-cpu-baseline $args > "$log" 2>&1
     rc=$?
     if [ $rc -ne 0 ]; then echo "$v rc=$rc" | tee -a "$OUT"; tail -5 "$log"; exit $rc; fi
     python3 - "$v" "$log" >> "$OUT" <<'EOF'

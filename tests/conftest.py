@@ -6,6 +6,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "physically-based-ray-tracer_amd"))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
+sys.path.insert(0, ROOT)  # bench.py, for the tests that import it (a bare `pytest` does not add the working directory)
 
 
 def pytest_configure(config):

@@ -23,6 +23,8 @@ The headline configs, through the same reference traversal (`make_golden.py ref`
   spaceship.npz        the textured Spaceship (scenes.config_spaceship) as data -- indexed mesh arrays, the three
                        1024x1024 maps as decoded texels, two instances, lights, sky, camera -- plus its
                        reference-traversal renders at 160x160: shaded (4 spp, depth 3), albedo and shading-normal views
+c4_ref_crop, c3_ref_480x270 and spaceship exceed 1 MiB as one file and are kept as <name>.part<k>.npz
+(helpers.save_fixture / load_fixture: the same arrays, bit for bit).
 Every fixture records a digest of the scene arrays it was made from, so a change of scenes.py is caught.
 
 usage: python tests/golden/make_golden.py [small] [inst] [ref] [ship]
@@ -40,7 +42,7 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import oracle  # noqa: E402
-from helpers import primary_dirs, random_rays  # noqa: E402
+from helpers import primary_dirs, random_rays, save_fixture  # noqa: E402
 from prt import scenes  # noqa: E402
 
 
@@ -141,9 +143,9 @@ def c4_ref_crop():
     x0, y0, w, h = C4_CROP
     a = avg.reshape(H, W, 4)[y0:y0 + h, x0:x0 + w, :3]
     r = rgb8.reshape(H, W)[y0:y0 + h, x0:x0 + w]
-    np.savez_compressed(os.path.join(HERE, "c4_ref_crop.npz"), W=W, H=H, spp=4, bounces=4, flags=oracle.DEFAULT_FLAGS,
-                        crop=np.array(C4_CROP), avg=a, rgb8=r, segments=int(st.segments),
-                        shadow_rays=int(st.shadow_rays), avg_sha=sha(avg), rgb8_sha=sha(rgb8), digest=scene_digest(sd))
+    save_fixture(os.path.join(HERE, "c4_ref_crop.npz"), W=W, H=H, spp=4, bounces=4, flags=oracle.DEFAULT_FLAGS,
+                 crop=np.array(C4_CROP), avg=a, rgb8=r, segments=int(st.segments),
+                 shadow_rays=int(st.shadow_rays), avg_sha=sha(avg), rgb8_sha=sha(rgb8), digest=scene_digest(sd))
     return int(st.segments), int(st.shadow_rays)
 
 
@@ -152,9 +154,9 @@ def c3_ref():
     sd = scenes.config_c3()
     W, H = 480, 270
     avg, rgb8, _, st = _ref_render(sd, W, H, 4, 4)
-    np.savez_compressed(os.path.join(HERE, "c3_ref_480x270.npz"), W=W, H=H, spp=4, bounces=4,
-                        flags=oracle.DEFAULT_FLAGS, avg=avg[:, :3].copy(), rgb8=rgb8, segments=int(st.segments),
-                        shadow_rays=int(st.shadow_rays), digest=scene_digest(sd))
+    save_fixture(os.path.join(HERE, "c3_ref_480x270.npz"), W=W, H=H, spp=4, bounces=4,
+                 flags=oracle.DEFAULT_FLAGS, avg=avg[:, :3].copy(), rgb8=rgb8, segments=int(st.segments),
+                 shadow_rays=int(st.shadow_rays), digest=scene_digest(sd))
     return int(st.segments), int(st.shadow_rays)
 
 
@@ -261,14 +263,14 @@ def spaceship():
         out[f"{name}_rgb8"] = rgb8
         out[f"{name}_counts"] = np.array([st.segments, st.shadow_rays], np.int64)
     L = sd.lights
-    np.savez_compressed(os.path.join(HERE, "spaceship.npz"), P=P, N=N, UV=UV, tri=tri.astype(np.int32),
-                        albedo=m.albedo, normal=m.normal, metalness=m.metalness, emission=m.emission,
-                        tex0=sd.textures[0], tex1=sd.textures[1], tex2=sd.textures[2],
-                        xf=np.stack([x for _, x in sd.instances]).astype(np.float32),
-                        xf_mesh=np.array([mi for mi, _ in sd.instances], np.int32),
-                        point_pos=L.point_pos, point_col=L.point_col, dir_pos=L.dir_pos, dir_col=L.dir_col,
-                        spot_pos=L.spot_pos, spot_col=L.spot_col, spot_rot=L.spot_rot, sky=sd.sky,
-                        cam_pos=sd.cam_pos, cam_target=sd.cam_target, W=W, H=H, digest=scene_digest(sd), **out)
+    save_fixture(os.path.join(HERE, "spaceship.npz"), P=P, N=N, UV=UV, tri=tri.astype(np.int32),
+                 albedo=m.albedo, normal=m.normal, metalness=m.metalness, emission=m.emission,
+                 tex0=sd.textures[0], tex1=sd.textures[1], tex2=sd.textures[2],
+                 xf=np.stack([x for _, x in sd.instances]).astype(np.float32),
+                 xf_mesh=np.array([mi for mi, _ in sd.instances], np.int32),
+                 point_pos=L.point_pos, point_col=L.point_col, dir_pos=L.dir_pos, dir_col=L.dir_col,
+                 spot_pos=L.spot_pos, spot_col=L.spot_col, spot_rot=L.spot_rot, sky=sd.sky,
+                 cam_pos=sd.cam_pos, cam_target=sd.cam_target, W=W, H=H, digest=scene_digest(sd), **out)
     return {k: v.tolist() for k, v in out.items() if k.endswith("counts")}
 
 

@@ -8,6 +8,71 @@ from prt import scenes
 RMSE_TOL = 1e-4  # BASELINE.json north star: per-channel RMSE <= 1e-4 vs the CPU reference
 
 
+FIXTURE_PART_BYTES = 900_000  # a committed file stays under 1 MiB: larger fixtures are kept as several parts
+
+
+def _npz_bytes(arrays):
+    import io
+    b = io.BytesIO()
+    np.savez_compressed(b, **arrays)
+    return b.getvalue()
+
+
+def save_fixture(path, **arrays):
+    """np.savez_compressed(path, **arrays) as <stem>.part<k>.npz files of at most FIXTURE_PART_BYTES each: an array
+    that compresses to more is cut along its first axis into pieces named <key>__<i>; load_fixture puts them
+    together.  Earlier parts of the same stem are replaced."""
+    import glob
+    import os
+    stem = path[:-4] if path.endswith(".npz") else path
+    pieces = []  # (key, array, compressed size)
+    for k, v in arrays.items():
+        v = np.asarray(v)
+        size = len(_npz_bytes({k: v}))
+        n = 1 if size <= FIXTURE_PART_BYTES // 2 or v.ndim == 0 else -(-size // (FIXTURE_PART_BYTES // 2))
+        for i, p in enumerate(np.array_split(v, n) if n > 1 else [v]):
+            key = f"{k}__{i}" if n > 1 else k
+            pieces.append((key, p, len(_npz_bytes({key: p}))))
+    parts, cur, cur_size = [], {}, 0
+    for key, p, size in pieces:
+        if cur and cur_size + size > FIXTURE_PART_BYTES:
+            parts.append(cur)
+            cur, cur_size = {}, 0
+        cur[key] = p
+        cur_size += size
+    parts.append(cur)
+    for f in glob.glob(glob.escape(stem) + ".part*.npz"):
+        os.remove(f)
+    for i, part in enumerate(parts):
+        data = _npz_bytes(part)
+        assert len(data) < (1 << 20), (stem, i, len(data))
+        with open(f"{stem}.part{i}.npz", "wb") as f:
+            f.write(data)
+    return len(parts)
+
+
+def load_fixture(path):
+    """The arrays of a fixture written by save_fixture, as a dict (allow_pickle=False: plain arrays only)."""
+    import glob
+    stem = path[:-4] if path.endswith(".npz") else path
+    files = sorted(glob.glob(glob.escape(stem) + ".part*.npz"))
+    assert files, f"{stem}.part*.npz: no such fixture"
+    flat = {}
+    for f in files:
+        with np.load(f) as z:
+            flat.update({k: z[k] for k in z.files})
+    out, cut = {}, {}
+    for k, v in flat.items():
+        base, sep, i = k.rpartition("__")
+        if sep and i.isdigit():
+            cut.setdefault(base, {})[int(i)] = v
+        else:
+            out[k] = v
+    for base, ps in cut.items():
+        out[base] = np.concatenate([ps[i] for i in range(len(ps))])
+    return out
+
+
 def rmse(a, b):
     d = np.asarray(a, np.float64)[:, :3] - np.asarray(b, np.float64)[:, :3]
     return float(np.sqrt(np.mean(d * d)))
