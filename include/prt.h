@@ -308,6 +308,49 @@ int prt_intersect(prt_ctx* ctx, int32_t n, const float* origins, const float* di
 int prt_occluded(prt_ctx* ctx, int32_t n, const float* origins, const float* dirs, const float* tmax,
                  int32_t* occluded);
 
+/* ---- first-hit feature buffers and the denoiser they guide (ABI 10, additive; DESIGN.md "Denoiser") ----
+ * Both calls first join the frames in flight and run on the context stream; with device pointers they do not wait
+ * on the host.  Their scratch buffers belong to the context.  On a sharded or group context they run over the whole
+ * image on the calling (member 0) device, with no collective. */
+
+/* (ABI 10, additive) First-hit feature buffers of the current scene and camera at pixel centres (the unjittered
+ * path-1 primary ray, Panini when post-processing is on).  Any output may be NULL; host pointers unless PRT_OUT_DEVICE.
+ *   albedo_rgba  float4 W*H: rgb = MaterialProperties::baseColor as PRT_MODE_BASECOLOR shows it, w = 1; miss: 0,0,0,0
+ *   normal_depth float4 W*H: xyz = the shading normal exactly as Trace uses it (NOT normalised in the smooth
+ *                branch, Core/Scene.cpp:134-136), w = primary hit t; miss: 0,0,0,1e30
+ * flags: only PRT_FLAG_NORMALMAP is read.  Does not touch the accumulation state or the ray totals.
+ * No scene or camera: PRT_ERR_NOT_READY. */
+int prt_render_aov(prt_ctx* ctx, int32_t width, int32_t height, uint32_t flags,
+                   float* albedo_rgba, float* normal_depth, uint32_t out_flags);
+
+/* (ABI 10, additive) Out of range (PRT_ERR_INVALID_ARGUMENT): iterations, normal_power, a negative or non-finite
+ * sigma, sigma_color or sigma_depth 0. */
+typedef struct {
+    int32_t iterations;     /* 1..8, step 2^i in iteration i                       default 5    */
+    int32_t normal_power;   /* log2 of the normal exponent, 0..7 (3 -> dot^8)      default 3    */
+    float sigma_color;      /* halves every iteration                              default 4.0  */
+    float sigma_depth;      /* relative depth change per pixel of tap distance     default 0.1  */
+    float sigma_albedo;     /* 0 = albedo not used as a guide                      default 0.25 */
+} prt_denoise_params;
+/* (ABI 10, additive) host only, no context */
+int prt_denoise_defaults(prt_denoise_params* out);
+
+/* (ABI 10, additive) Edge-avoiding a-trous filter of a W*H float4 image (prt_render's avg_rgba) guided by
+ * prt_render_aov's buffers.  out_rgba (w copied from the input) and out_rgb8 (RGBF32_to_RGB8 of out, no screen pass)
+ * may each be NULL, not both; out_rgba may be color_rgba itself.  albedo_rgba may be NULL when sigma_albedo is 0.
+ * All pointers host, or all device with PRT_OUT_DEVICE. */
+int prt_denoise(prt_ctx* ctx, const prt_denoise_params* params, int32_t width, int32_t height, const float* color_rgba,
+                const float* albedo_rgba, const float* normal_depth, float* out_rgba, uint32_t* out_rgb8,
+                uint32_t out_flags);
+
+/* (ABI 10, additive) With PRT_OUT_TIMED in out_flags, prt_render_aov and prt_denoise record HIP events around their
+ * passes; prt_denoise_timings waits for the context stream and returns the device times in ms of the last timed
+ * calls: ms[0] the AOV pass (primary hits + attributes), ms[1] the denoiser's prep pass, ms[2 + i] filter iteration i.
+ * count = 1..PRT_DENOISE_TIMINGS; entries that did not run are 0. */
+#define PRT_OUT_TIMED (1u << 1)
+#define PRT_DENOISE_TIMINGS 10
+int prt_denoise_timings(prt_ctx* ctx, float* ms, int32_t count);
+
 /* ---- shading-function probe (ABI 10): the device's own BRDF functions (the ones the shading kernels inline) on
  * n host records, for known-answer tests of the BRDF restatement (Core/BRDF.cpp).  Record k: in[24 k ..], out[8 k ..].
  *   EVAL         BRDF::evalCombinedBRDF (:439-452)     in N[0..2] L[3..5] V[6..8] material[9..16]    out rgb[0..2]

@@ -282,6 +282,35 @@ class Renderer {
     check(prt_ray_totals(ctx_, segments, shadow_rays, reset ? 1 : 0));
   }
 
+  // First-hit feature buffers of the scene and camera at pixel centres (prt_render_aov): albedo = base colour
+  // (w = 1; miss 0), normal_depth = the shading normal as Trace uses it with the hit distance in w (miss
+  // 0,0,0,1e30); float4 x W*H each.  The accumulation and the ray totals stay as they are.
+  void Aov(std::vector<float>& albedo, std::vector<float>& normal_depth) {
+    albedo.assign(4 * (size_t)width_ * height_, 0.0f);
+    normal_depth.assign(4 * (size_t)width_ * height_, 0.0f);
+    const prt_postfx pf = camera.PostFx(isPostProcessed);  // the primary rays follow Tick's (Panini)
+    check(prt_set_postfx(ctx_, &pf));
+    check(prt_render_aov(ctx_, width_, height_, NORMALMAPPED ? PRT_FLAG_NORMALMAP : 0u, albedo.data(),
+                         normal_depth.data(), 0u));
+  }
+  static prt_denoise_params DenoiseDefaults() {
+    prt_denoise_params p{};
+    check(prt_denoise_defaults(&p));
+    return p;
+  }
+  // The current average (accumulator) filtered by the edge-avoiding a-trous denoiser with fresh AOVs (prt_denoise):
+  // average gets the float4 image, screen8 its 0x00RRGGBB pixels (no screen pass).  accumulator, screen and the
+  // accumulation stay as Tick() left them, so it can be called after any Tick.
+  void Denoise(std::vector<float>& average, std::vector<uint32_t>& screen8,
+               const prt_denoise_params& params = DenoiseDefaults()) {
+    std::vector<float> albedo, normal_depth;
+    Aov(albedo, normal_depth);
+    average.assign(accumulator.size(), 0.0f);
+    screen8.assign(screen.size(), 0u);
+    check(prt_denoise(ctx_, &params, width_, height_, accumulator.data(), albedo.data(), normal_depth.data(),
+                      average.data(), screen8.data(), 0u));
+  }
+
   uint32_t Flags() const {
     return (AA ? PRT_FLAG_AA : 0u) | (accumulates ? PRT_FLAG_ACCUMULATE : 0u) | (GAMMACORRECTED ? PRT_FLAG_GAMMA : 0u) |
            (NORMALMAPPED ? PRT_FLAG_NORMALMAP : 0u) | (SKYBOX ? PRT_FLAG_SKYBOX : 0u) | (LIGHTED ? PRT_FLAG_LIGHTED : 0u) |

@@ -20,6 +20,7 @@
 #include "../../include/prt.h"
 #include "bvh_build.h"
 #include "bvh_gpu.h"
+#include "prt_denoise.h"
 #include "prt_launch.h"
 #include "prt_rccl.h"
 #include "prt_refit.h"
@@ -324,6 +325,12 @@ struct prt_ctx {
   Flight fl[kMaxFlights];
   int32_t next_fl = 0, last_fl = -1;  // the slot of the next call / of the last call still ordering accumulation
   hipEvent_t fl_fork = nullptr;
+  // first-hit AOVs and the denoiser (prt_render_aov / prt_denoise): primary hits, staging of host inputs / outputs,
+  // the packed unit normal + depth, and the two buffers the filter iterations alternate between
+  DevBuf aov_hits, aov_alb, aov_nd;
+  DevBuf dn_in[3], dn_geo, dn_pp[2], dn_out, dn_rgb8;
+  hipEvent_t dn_ev[2 + PRT_DENOISE_TIMINGS] = {};  // PRT_OUT_TIMED: [0..1] the AOV pass, [2..] prep + iterations
+  int32_t dn_timed_aov = 0, dn_timed_passes = 0;   // what the last timed calls recorded
 };
 
 namespace {
@@ -1527,6 +1534,8 @@ int prt_destroy(prt_ctx* c) {
     if (e) (void)hipEventDestroy(e);
   for (auto e : c->wt.ev)
     if (e) (void)hipEventDestroy(e);
+  for (auto e : c->dn_ev)
+    if (e) (void)hipEventDestroy(e);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;  // DevBuf members free their device memory
   return PRT_OK;
@@ -2173,6 +2182,149 @@ int prt_intersect(prt_ctx* c, int32_t n, const float* O, const float* D, const f
 }
 int prt_occluded(prt_ctx* c, int32_t n, const float* O, const float* D, const float* tmax, int32_t* occ) {
   return ray_query(c, n, O, D, tmax, occ, true);
+}
+
+// ---- first-hit AOVs and the a-trous denoiser (prt_denoise.hip)
+namespace {
+int dn_event(prt_ctx* c, int k) {  // record timing event k on the context stream
+  if (!c->dn_ev[k]) HIP_TRY(hipEventCreate(&c->dn_ev[k]));
+  HIP_TRY(hipEventRecord(c->dn_ev[k], c->stream));
+  return PRT_OK;
+}
+bool sigma_ok(float v, bool zero_ok) { return std::isfinite(v) && (zero_ok ? v >= 0.0f : v > 0.0f); }
+}  // namespace
+
+int prt_render_aov(prt_ctx* c, int32_t W, int32_t H, uint32_t flags, float* albedo, float* normal_depth,
+                   uint32_t out_flags) {
+  if (!c || W <= 0 || H <= 0 || W > 16384 || H > 16384) return fail(PRT_ERR_INVALID_ARGUMENT, "bad AOV arguments");
+  PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
+  HIP_TRY(hipSetDevice(c->device));
+  SceneDev S;
+  int rc = scene_ready(c, S);
+  if (rc) return rc;
+  if (!c->have_camera) return fail(PRT_ERR_NOT_READY, "no camera");
+  if (!depth_ok(c)) return fail(PRT_ERR_UNSUPPORTED, "BVH deeper than 64 levels");
+  if (!albedo && !normal_depth) return PRT_OK;
+  const TileMap M = make_tilemap(W, H, 8, 0, 1);
+  const size_t n = (size_t)W * H;
+  rc = ensure_spill(c, S, (size_t)M.items + 256);
+  if (rc) return rc;
+  const bool dev_out = (out_flags & PRT_OUT_DEVICE) != 0, timed = (out_flags & PRT_OUT_TIMED) != 0;
+  HIP_TRY(c->aov_hits.ensure(n * sizeof(HitOut)));
+  HIP_TRY(c->counters.ensure(sizeof(Counters)));  // the launch's own ray count: not the running totals
+  float4* a = reinterpret_cast<float4*>(albedo);
+  float4* g = reinterpret_cast<float4*>(normal_depth);
+  if (!dev_out) {
+    if (albedo) { HIP_TRY(c->aov_alb.ensure(n * sizeof(float4))); a = c->aov_alb.as<float4>(); }
+    if (normal_depth) { HIP_TRY(c->aov_nd.ensure(n * sizeof(float4))); g = c->aov_nd.as<float4>(); }
+  }
+  LaunchCfg L{c->stream, occ_for(c)};
+  if (timed && (rc = dn_event(c, 0))) return rc;
+  HIP_TRY(launch_primary_hits(L, S, M, c->aov_hits.as<HitOut>(), c->counters.as<Counters>()));
+  HIP_TRY(launch_aov(c->stream, S, W, H, (flags & PRT_FLAG_NORMALMAP) != 0, c->aov_hits.as<HitOut>(), a, g));
+  if (timed) {
+    if ((rc = dn_event(c, 1))) return rc;
+    c->dn_timed_aov = 1;
+  }
+  if (!dev_out) {
+    if (albedo) HIP_TRY(hipMemcpyAsync(albedo, a, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    if (normal_depth) HIP_TRY(hipMemcpyAsync(normal_depth, g, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  return PRT_OK;
+}
+
+int prt_denoise_defaults(prt_denoise_params* out) {
+  if (!out) return fail(PRT_ERR_INVALID_ARGUMENT, "out is NULL");
+  out->iterations = 5;
+  out->normal_power = 3;
+  out->sigma_color = 4.0f;
+  out->sigma_depth = 0.1f;
+  out->sigma_albedo = 0.25f;
+  return PRT_OK;
+}
+
+int prt_denoise(prt_ctx* c, const prt_denoise_params* p, int32_t W, int32_t H, const float* color, const float* albedo,
+                const float* normal_depth, float* out_rgba, uint32_t* out_rgb8, uint32_t out_flags) {
+  if (!c || !p || !color || !normal_depth || (!out_rgba && !out_rgb8) || W <= 0 || H <= 0 || W > 16384 || H > 16384)
+    return fail(PRT_ERR_INVALID_ARGUMENT, "bad denoise arguments");
+  if (p->iterations < 1 || p->iterations > 8 || p->normal_power < 0 || p->normal_power > 7 ||
+      !sigma_ok(p->sigma_color, false) || !sigma_ok(p->sigma_depth, false) || !sigma_ok(p->sigma_albedo, true))
+    return fail(PRT_ERR_INVALID_ARGUMENT, "denoise parameters out of range");
+  const bool use_albedo = p->sigma_albedo > 0.0f;
+  if (use_albedo && !albedo) return fail(PRT_ERR_INVALID_ARGUMENT, "albedo is NULL with sigma_albedo > 0");
+  PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t n = (size_t)W * H, bytes = n * sizeof(float4);
+  const bool dev = (out_flags & PRT_OUT_DEVICE) != 0, timed = (out_flags & PRT_OUT_TIMED) != 0;
+  const float4* src[3] = {reinterpret_cast<const float4*>(color), reinterpret_cast<const float4*>(normal_depth),
+                          use_albedo ? reinterpret_cast<const float4*>(albedo) : nullptr};
+  float4* dst = reinterpret_cast<float4*>(out_rgba);
+  uint32_t* dst8 = out_rgb8;
+  if (!dev) {  // host images: staged in context buffers
+    for (int k = 0; k < 3; k++) {
+      if (!src[k]) continue;
+      HIP_TRY(c->dn_in[k].ensure(bytes));
+      HIP_TRY(hipMemcpyAsync(c->dn_in[k].p, src[k], bytes, hipMemcpyHostToDevice, c->stream));
+      src[k] = c->dn_in[k].as<float4>();
+    }
+    if (out_rgba) { HIP_TRY(c->dn_out.ensure(bytes)); dst = c->dn_out.as<float4>(); }
+    if (out_rgb8) { HIP_TRY(c->dn_rgb8.ensure(n * 4)); dst8 = c->dn_rgb8.as<uint32_t>(); }
+  }
+  HIP_TRY(c->dn_geo.ensure(bytes));
+  if (p->iterations > 1 || dst == src[0]) {
+    HIP_TRY(c->dn_pp[0].ensure(bytes));
+    if (p->iterations > 2) HIP_TRY(c->dn_pp[1].ensure(bytes));
+  }
+  int rc = PRT_OK;
+  if (timed && (rc = dn_event(c, 2))) return rc;
+  HIP_TRY(launch_denoise_prep(c->stream, W, H, src[1], c->dn_geo.as<float4>()));
+  if (timed && (rc = dn_event(c, 3))) return rc;
+  const float4* in = src[0];
+  if (p->iterations == 1 && dst == in) {  // a single pass in place: filter a copy
+    HIP_TRY(hipMemcpyAsync(c->dn_pp[0].p, in, bytes, hipMemcpyDeviceToDevice, c->stream));
+    in = c->dn_pp[0].as<float4>();
+  }
+  for (int32_t i = 0; i < p->iterations; i++) {
+    const bool last = i == p->iterations - 1;
+    const float sc = p->sigma_color * std::ldexp(1.0f, -i);
+    DenoisePass P{};
+    P.W = W;
+    P.H = H;
+    P.step = 1 << i;
+    P.normal_power = p->normal_power;
+    P.sc2 = sc * sc;
+    P.sigma_depth = p->sigma_depth;
+    P.sa2 = p->sigma_albedo * p->sigma_albedo;
+    P.color = in;
+    P.geo = c->dn_geo.as<float4>();
+    P.albedo = src[2];
+    P.out = last ? dst : c->dn_pp[i & 1].as<float4>();
+    P.rgb8 = last ? dst8 : nullptr;
+    HIP_TRY(launch_denoise_pass(c->stream, P));
+    if (timed && (rc = dn_event(c, 4 + i))) return rc;
+    in = P.out;
+  }
+  if (timed) c->dn_timed_passes = p->iterations;
+  if (!dev) {
+    if (out_rgba) HIP_TRY(hipMemcpyAsync(out_rgba, dst, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (out_rgb8) HIP_TRY(hipMemcpyAsync(out_rgb8, dst8, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  return PRT_OK;
+}
+
+int prt_denoise_timings(prt_ctx* c, float* ms, int32_t count) {
+  if (!c || !ms || count < 1 || count > PRT_DENOISE_TIMINGS) return fail(PRT_ERR_INVALID_ARGUMENT, "bad timing arguments");
+  PRT_JOIN(c);
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  float t[PRT_DENOISE_TIMINGS] = {};
+  if (c->dn_timed_aov) HIP_TRY(hipEventElapsedTime(&t[0], c->dn_ev[0], c->dn_ev[1]));
+  for (int32_t k = 0; c->dn_timed_passes > 0 && k < 1 + c->dn_timed_passes; k++)
+    HIP_TRY(hipEventElapsedTime(&t[1 + k], c->dn_ev[2 + k], c->dn_ev[3 + k]));
+  for (int32_t k = 0; k < count; k++) ms[k] = t[k];
+  return PRT_OK;
 }
 
 int prt_brdf_probe(prt_ctx* c, int32_t op, int32_t n, const float* in, float* out) {

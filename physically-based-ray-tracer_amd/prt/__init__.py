@@ -3,8 +3,9 @@ Renderer / Scene / Camera API; compute in hand-written HIP kernels behind includ
 from . import scenes, tiles
 from ._lib import (FLAGS_DEFAULT, FLAG_AA, FLAG_ACCUMULATE, FLAG_GAMMA, FLAG_LIGHTED, FLAG_NORMALMAP, FLAG_SKYBOX,
                    FLAG_STOCHASTIC, PrtError, load)
-from .renderer import Camera, Context, LightTransform, Renderer, Scene, postfx_preset
+from .renderer import Camera, Context, LightTransform, Renderer, Scene, denoise_defaults, postfx_preset
 
 __all__ = ["scenes", "tiles", "load", "PrtError", "Camera", "Context", "LightTransform", "Renderer", "Scene",
+           "denoise_defaults", "postfx_preset",
            "FLAGS_DEFAULT", "FLAG_AA", "FLAG_ACCUMULATE", "FLAG_GAMMA", "FLAG_LIGHTED", "FLAG_NORMALMAP",
            "FLAG_SKYBOX", "FLAG_STOCHASTIC"]

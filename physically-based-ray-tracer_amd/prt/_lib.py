@@ -14,6 +14,8 @@ ABI_VERSION = 10  # PRT_ABI_VERSION of the include/prt.h these structs mirror
 FLAG_AA, FLAG_ACCUMULATE, FLAG_GAMMA, FLAG_NORMALMAP, FLAG_SKYBOX, FLAG_LIGHTED, FLAG_STOCHASTIC = (1 << i for i in range(7))
 FLAGS_DEFAULT = 0x7F
 OUT_DEVICE = 1
+OUT_TIMED = 2  # prt_render_aov / prt_denoise: record the per-pass HIP events prt_denoise_timings reads
+DENOISE_TIMINGS = 10
 BUILDER_HOST_SAH, BUILDER_GPU_LBVH, BUILDER_HOST_SBVH, BUILDER_GPU_PLOC = 0, 1, 2, 3
 
 # Renderer::RENDER_STATES (Core/Renderer.h:37-46)
@@ -29,6 +31,7 @@ EXPORTS = [
     "prt_set_instance_materials", "prt_set_area_lights", "prt_shard_unique_id", "prt_shard_init_rccl",
     "prt_shard_attach_rccl", "prt_create_group", "prt_get_shard_info", "prt_accumulation_bytes",
     "prt_save_accumulation", "prt_load_accumulation", "prt_ray_totals", "prt_set_frames_in_flight", "prt_finish",
+    "prt_render_aov", "prt_denoise_defaults", "prt_denoise", "prt_denoise_timings",
 ]
 SHARD_ID_BYTES = 128
 SHARD_NONE, SHARD_RCCL, SHARD_GROUP = 0, 1, 2  # prt_shard_info.transport
@@ -93,6 +96,12 @@ class Stats(C.Structure):
 
 class Hit(C.Structure):
     _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("prim", C.c_uint32), ("inst", C.c_uint32)]
+
+
+class DenoiseParams(C.Structure):
+    """prt_denoise_params: iterations 1..8, normal_power 0..7 (log2 of the normal exponent), the three sigmas."""
+    _fields_ = [("iterations", C.c_int32), ("normal_power", C.c_int32), ("sigma_color", C.c_float),
+                ("sigma_depth", C.c_float), ("sigma_albedo", C.c_float)]
 
 
 class ShardInfo(C.Structure):
@@ -165,6 +174,10 @@ def load():
         "prt_shard_attach_rccl": ([vp, vp, i32], C.c_int),
         "prt_create_group": ([C.POINTER(DeviceDesc), i32, i32, C.POINTER(vp)], C.c_int),
         "prt_get_shard_info": ([vp, C.POINTER(ShardInfo)], C.c_int),
+        "prt_render_aov": ([vp, i32, i32, u32, vp, vp, u32], C.c_int),
+        "prt_denoise_defaults": ([C.POINTER(DenoiseParams)], C.c_int),
+        "prt_denoise": ([vp, C.POINTER(DenoiseParams), i32, i32, vp, vp, vp, vp, vp, u32], C.c_int),
+        "prt_denoise_timings": ([vp, C.POINTER(C.c_float), i32], C.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

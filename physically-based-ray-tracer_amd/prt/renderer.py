@@ -81,6 +81,18 @@ def postfx_preset(preset=0, **overrides):
     return pf
 
 
+def denoise_defaults(**overrides):
+    """prt_denoise_params at the library's defaults (prt_denoise_defaults); keyword overrides set single fields
+    (iterations, normal_power, sigma_color, sigma_depth, sigma_albedo)."""
+    dp = _lib.DenoiseParams()
+    check(_lib.load().prt_denoise_defaults(C.byref(dp)))
+    for k, v in overrides.items():
+        if k not in dict(dp._fields_):
+            raise TypeError(f"prt_denoise_params has no field {k!r}")
+        setattr(dp, k, v)
+    return dp
+
+
 class Scene:
     """Scene (Core/Scene.h): models, BLAS instances (gameobject -> modelIndex + transform), lights, sky."""
 
@@ -306,6 +318,49 @@ class Context:
         check(self.L.prt_trace_primary(self.h, width, height, hits.ctypes.data, 0, C.byref(st)))
         return hits, _checked(st)
 
+    # -- first-hit feature buffers and the denoiser they guide (include/prt.h prt_render_aov / prt_denoise)
+    def render_aov(self, width, height, flags=_lib.FLAG_NORMALMAP, device_out=False, albedo=None, normal_depth=None,
+                   timed=False):
+        """(albedo[n,4], normal_depth[n,4]) of the first hit at pixel centres: base colour (w = 1; miss 0) and the
+        shading normal as Trace uses it with the hit distance in w (miss 0,0,0,1e30).  The accumulation and the ray
+        totals stay as they are.  device_out: albedo / normal_depth are raw device pointers (either may be None)."""
+        n = width * height
+        if not device_out:
+            albedo = np.zeros((n, 4), F32)
+            normal_depth = np.zeros((n, 4), F32)
+            pa, pn = albedo.ctypes.data, normal_depth.ctypes.data
+        else:
+            pa, pn = albedo, normal_depth
+        of = (_lib.OUT_DEVICE if device_out else 0) | (_lib.OUT_TIMED if timed else 0)
+        check(self.L.prt_render_aov(self.h, width, height, flags, pa, pn, of))
+        return albedo, normal_depth
+
+    def denoise(self, color, albedo, normal_depth, width, height, params=None, device_out=False, out=None, rgb8=None,
+                timed=False):
+        """Edge-avoiding a-trous filter of `color` (float4 per pixel, render()'s avg) guided by render_aov()'s
+        buffers; returns (out[n,4], rgb8[n]).  device_out: every image is a raw device pointer, out / rgb8 are
+        where the results go (either may be None; out may be the same pointer as color) and no host wait happens."""
+        dp = params if params is not None else denoise_defaults()
+        n = width * height
+        of = (_lib.OUT_DEVICE if device_out else 0) | (_lib.OUT_TIMED if timed else 0)
+        if not device_out:
+            color, normal_depth = _f32(color).reshape(n, 4), _f32(normal_depth).reshape(n, 4)
+            albedo = _f32(albedo).reshape(n, 4) if albedo is not None else None
+            out = np.zeros((n, 4), F32)
+            rgb8 = np.zeros(n, np.uint32)
+            args = (color.ctypes.data, albedo.ctypes.data if albedo is not None else None, normal_depth.ctypes.data,
+                    out.ctypes.data, rgb8.ctypes.data)
+        else:
+            args = (color, albedo, normal_depth, out, rgb8)
+        check(self.L.prt_denoise(self.h, C.byref(dp), width, height, *args, of))
+        return out, rgb8
+
+    def denoise_timings(self):
+        """Device ms of the last timed=True calls: [AOV pass, denoiser prep, filter iteration 0, 1, ...]."""
+        ms = (C.c_float * _lib.DENOISE_TIMINGS)()
+        check(self.L.prt_denoise_timings(self.h, ms, _lib.DENOISE_TIMINGS))
+        return [float(v) for v in ms]
+
     def intersect(self, O, D, tmax=None):
         O, D = _f32(O), _f32(D)
         n = O.shape[0]
@@ -410,6 +465,15 @@ class Renderer:
         self.frame += frames
         self.last_stats = st
         return st
+
+    def Denoise(self, params=None):
+        """The current average filtered by the a-trous denoiser with fresh first-hit AOVs of the scene and camera:
+        returns (average, screen) of the denoised image.  self.average, self.screen and the accumulation stay as
+        Tick() left them, so progressive rendering continues undisturbed."""
+        flags = _lib.FLAG_NORMALMAP if self.NORMALMAPPED else 0
+        self.ctx.set_postfx(self.camera.postfx(self.isPostProcessed))  # the AOV primary rays follow Tick's (Panini)
+        alb, nd = self.ctx.render_aov(self.width, self.height, flags)
+        return self.ctx.denoise(self.average, alb, nd, self.width, self.height, params)
 
     def Capture(self, path):
         """Renderer::Capture (Core/Renderer.cpp:437-465): the screen as a PNG (the reference names it by time)."""
