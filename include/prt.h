@@ -351,6 +351,46 @@ int prt_denoise(prt_ctx* ctx, const prt_denoise_params* params, int32_t width, i
 #define PRT_DENOISE_TIMINGS 10
 int prt_denoise_timings(prt_ctx* ctx, float* ms, int32_t count);
 
+/* ---- temporal reprojection of the frame history under camera motion (ABI 10, additive; DESIGN.md "Temporal
+ * reprojection") ----
+ * (ABI 10, additive) Out of range (PRT_ERR_INVALID_ARGUMENT): a negative or non-finite depth_tol, a normal_min outside
+ * [-1, 1] or non-finite, a max_history that is non-finite or below 1. */
+typedef struct {
+    float depth_tol;     /* relative depth difference a history tap may have      default 0.05 */
+    float normal_min;    /* least dot of the unit normals of pixel and tap        default 0.9  */
+    float max_history;   /* cap of the history length, >= 1                       default 16   */
+} prt_reproject_params;
+/* (ABI 10, additive) host only, no context */
+int prt_reproject_defaults(prt_reproject_params* out);
+
+/* (ABI 10, additive) One stateless pass: the first hit of every pixel of this view is projected into the previous
+ * view, the previous output is gathered there with bilinear weights from the taps whose depth and unit normal agree
+ * (depth_tol, normal_min) and whose history length is >= 1, and this frame is blended in with weight 1 / length,
+ * length = min(gathered length + 1, max_history).  A miss, a point behind or off the previous screen, or taps of
+ * total weight <= 1/64 start over: out = (color.rgb, 1).
+ *   color_rgba            this frame's image (prt_render's avg_rgba; its w is ignored)
+ *   normal_depth          this view's prt_render_aov buffer
+ *   camera                this view's camera
+ *   prev_camera           the previous view's camera
+ *   history_rgba          a previous out_rgba: rgb = the history, w = its length.  A raw avg_rgba (w = 0) is rejected
+ *                         tap by tap and so behaves as no history
+ *   history_normal_depth  the previous view's prt_render_aov buffer
+ * The three prev / history arguments are all NULL (a history starts: out = (color.rgb, 1)) or all given; a mix is
+ * PRT_ERR_INVALID_ARGUMENT.  out_rgba (w = the new history length) and out_rgb8 (RGBF32_to_RGB8 of out, no screen
+ * pass) may each be NULL, not both.  out_rgba may be color_rgba; it must not be history_rgba or
+ * history_normal_depth (neighbouring pixels are gathered): PRT_ERR_INVALID_ARGUMENT.
+ * All image pointers host, or all device with PRT_OUT_DEVICE; the cameras are always host structs.  Like prt_denoise
+ * the call joins the frames in flight, runs on the context stream, does not wait on the host with device pointers,
+ * stages host images through context buffers, touches neither the accumulation state nor the ray totals, and on a
+ * sharded or group context runs over the whole image on member 0's device.
+ * Defined for the plane projection only: with Panini primary rays (post-processing on) the cameras do not describe
+ * the rays, and this call cannot know -- the caller must not use it then (the Renderer mirrors refuse).  Moving
+ * instances are not tracked: their pixels are rejected by the depth and normal tests, or ghost. */
+int prt_reproject(prt_ctx* ctx, const prt_reproject_params* params, int32_t width, int32_t height,
+                  const prt_camera* camera, const float* color_rgba, const float* normal_depth,
+                  const prt_camera* prev_camera, const float* history_rgba, const float* history_normal_depth,
+                  float* out_rgba, uint32_t* out_rgb8, uint32_t out_flags);
+
 /* ---- shading-function probe (ABI 10): the device's own BRDF functions (the ones the shading kernels inline) on
  * n host records, for known-answer tests of the BRDF restatement (Core/BRDF.cpp).  Record k: in[24 k ..], out[8 k ..].
  *   EVAL         BRDF::evalCombinedBRDF (:439-452)     in N[0..2] L[3..5] V[6..8] material[9..16]    out rgb[0..2]

@@ -311,6 +311,41 @@ class Renderer {
                       average.data(), screen8.data(), 0u));
   }
 
+  static prt_reproject_params ReprojectDefaults() {
+    prt_reproject_params p{};
+    check(prt_reproject_defaults(&p));
+    return p;
+  }
+  // One Tick() that stands alone (the accumulation is reset in full first, and the camera handed over, so a moved
+  // camera needs no CameraMoved()), reprojected onto the history this renderer keeps: the previous call's output,
+  // AOVs and camera (prt_reproject).  history gets the float4 image with the history length in w, screen8 its
+  // 0x00RRGGBB pixels (no screen pass); accumulator and screen are as Tick() left them.  The first call or
+  // ResetTemporal() starts a new history.  Throws with isPostProcessed: Panini primary rays are not described by
+  // the camera.
+  void TickTemporal(std::vector<float>& history, std::vector<uint32_t>& screen8,
+                    const prt_reproject_params& params = ReprojectDefaults()) {
+    if (isPostProcessed)
+      throw Error(PRT_ERR_INVALID_ARGUMENT,
+                  "temporal reprojection is defined for the plane projection only (isPostProcessed is set)");
+    const prt_camera cam = camera.Plane();
+    check(prt_set_camera(ctx_, &cam));
+    check(prt_reset_accumulation(ctx_, 1));
+    Tick();
+    std::vector<float> albedo, normal_depth;
+    Aov(albedo, normal_depth);
+    std::vector<float> out(accumulator.size(), 0.0f);
+    screen8.assign(screen.size(), 0u);
+    const bool have = !hist_.empty();
+    check(prt_reproject(ctx_, &params, width_, height_, &cam, accumulator.data(), normal_depth.data(),
+                        have ? &hist_cam_ : nullptr, have ? hist_.data() : nullptr, have ? hist_nd_.data() : nullptr,
+                        out.data(), screen8.data(), 0u));
+    hist_ = out;
+    hist_nd_.swap(normal_depth);
+    hist_cam_ = cam;
+    history.swap(out);
+  }
+  void ResetTemporal() { hist_.clear(); }  // the next TickTemporal() starts a new history
+
   uint32_t Flags() const {
     return (AA ? PRT_FLAG_AA : 0u) | (accumulates ? PRT_FLAG_ACCUMULATE : 0u) | (GAMMACORRECTED ? PRT_FLAG_GAMMA : 0u) |
            (NORMALMAPPED ? PRT_FLAG_NORMALMAP : 0u) | (SKYBOX ? PRT_FLAG_SKYBOX : 0u) | (LIGHTED ? PRT_FLAG_LIGHTED : 0u) |
@@ -326,6 +361,8 @@ class Renderer {
   int32_t width_, height_;
   uint32_t frame_ = 0;
   prt_stats stats_{};
+  std::vector<float> hist_, hist_nd_;  // TickTemporal's history: previous output, previous normal_depth (empty: none)
+  prt_camera hist_cam_{};              // ... and the camera they were made with
 };
 
 }  // namespace prt

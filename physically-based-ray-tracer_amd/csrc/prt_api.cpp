@@ -24,6 +24,7 @@
 #include "prt_launch.h"
 #include "prt_rccl.h"
 #include "prt_refit.h"
+#include "prt_temporal.h"
 
 using namespace prt;
 
@@ -331,6 +332,8 @@ struct prt_ctx {
   DevBuf dn_in[3], dn_geo, dn_pp[2], dn_out, dn_rgb8;
   hipEvent_t dn_ev[2 + PRT_DENOISE_TIMINGS] = {};  // PRT_OUT_TIMED: [0..1] the AOV pass, [2..] prep + iterations
   int32_t dn_timed_aov = 0, dn_timed_passes = 0;   // what the last timed calls recorded
+  // temporal reprojection (prt_reproject): staging of host images (colour, normal_depth, history, its normal_depth)
+  DevBuf rp_in[4], rp_out, rp_rgb8;
 };
 
 namespace {
@@ -2324,6 +2327,69 @@ int prt_denoise_timings(prt_ctx* c, float* ms, int32_t count) {
   for (int32_t k = 0; c->dn_timed_passes > 0 && k < 1 + c->dn_timed_passes; k++)
     HIP_TRY(hipEventElapsedTime(&t[1 + k], c->dn_ev[2 + k], c->dn_ev[3 + k]));
   for (int32_t k = 0; k < count; k++) ms[k] = t[k];
+  return PRT_OK;
+}
+
+// ---- temporal reprojection (prt_temporal.hip)
+int prt_reproject_defaults(prt_reproject_params* out) {
+  if (!out) return fail(PRT_ERR_INVALID_ARGUMENT, "out is NULL");
+  out->depth_tol = 0.05f;
+  out->normal_min = 0.9f;
+  out->max_history = 16.0f;
+  return PRT_OK;
+}
+
+int prt_reproject(prt_ctx* c, const prt_reproject_params* p, int32_t W, int32_t H, const prt_camera* cam,
+                  const float* color, const float* normal_depth, const prt_camera* prev_cam, const float* history,
+                  const float* history_nd, float* out_rgba, uint32_t* out_rgb8, uint32_t out_flags) {
+  if (!c || !p || !cam || !color || !normal_depth || (!out_rgba && !out_rgb8) || W <= 0 || H <= 0 || W > 16384 ||
+      H > 16384)
+    return fail(PRT_ERR_INVALID_ARGUMENT, "bad reproject arguments");
+  if (!sigma_ok(p->depth_tol, true) || !(p->normal_min >= -1.0f && p->normal_min <= 1.0f) ||
+      !std::isfinite(p->max_history) || p->max_history < 1.0f)
+    return fail(PRT_ERR_INVALID_ARGUMENT, "reproject parameters out of range");
+  const int given = (prev_cam ? 1 : 0) + (history ? 1 : 0) + (history_nd ? 1 : 0);
+  if (given != 0 && given != 3)
+    return fail(PRT_ERR_INVALID_ARGUMENT, "prev_camera, history_rgba and history_normal_depth go together");
+  if (out_rgba && given && (out_rgba == history || out_rgba == history_nd))
+    return fail(PRT_ERR_INVALID_ARGUMENT, "out_rgba must not be a history buffer");
+  PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t n = (size_t)W * H, bytes = n * sizeof(float4);
+  const bool dev = (out_flags & PRT_OUT_DEVICE) != 0;
+  const float4* src[4] = {reinterpret_cast<const float4*>(color), reinterpret_cast<const float4*>(normal_depth),
+                          reinterpret_cast<const float4*>(history), reinterpret_cast<const float4*>(history_nd)};
+  float4* dst = reinterpret_cast<float4*>(out_rgba);
+  uint32_t* dst8 = out_rgb8;
+  if (!dev) {  // host images: staged in context buffers
+    for (int k = 0; k < 4; k++) {
+      if (!src[k]) continue;
+      HIP_TRY(c->rp_in[k].ensure(bytes));
+      HIP_TRY(hipMemcpyAsync(c->rp_in[k].p, src[k], bytes, hipMemcpyHostToDevice, c->stream));
+      src[k] = c->rp_in[k].as<float4>();
+    }
+    if (out_rgba) { HIP_TRY(c->rp_out.ensure(bytes)); dst = c->rp_out.as<float4>(); }
+    if (out_rgb8) { HIP_TRY(c->rp_rgb8.ensure(n * 4)); dst8 = c->rp_rgb8.as<uint32_t>(); }
+  }
+  ReprojectPass P{};
+  P.W = W;
+  P.H = H;
+  P.depth_tol = p->depth_tol;
+  P.normal_min = p->normal_min;
+  P.max_history = p->max_history;
+  make_reproject_pass(P, *cam, prev_cam);
+  P.color = src[0];
+  P.nd = src[1];
+  P.hist = src[2];
+  P.hist_nd = src[3];
+  P.out = dst;
+  P.rgb8 = dst8;
+  HIP_TRY(launch_reproject(c->stream, P));
+  if (!dev) {
+    if (out_rgba) HIP_TRY(hipMemcpyAsync(out_rgba, dst, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (out_rgb8) HIP_TRY(hipMemcpyAsync(out_rgb8, dst8, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
   return PRT_OK;
 }
 

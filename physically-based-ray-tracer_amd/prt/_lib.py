@@ -32,6 +32,7 @@ EXPORTS = [
     "prt_shard_attach_rccl", "prt_create_group", "prt_get_shard_info", "prt_accumulation_bytes",
     "prt_save_accumulation", "prt_load_accumulation", "prt_ray_totals", "prt_set_frames_in_flight", "prt_finish",
     "prt_render_aov", "prt_denoise_defaults", "prt_denoise", "prt_denoise_timings",
+    "prt_reproject_defaults", "prt_reproject",
 ]
 SHARD_ID_BYTES = 128
 SHARD_NONE, SHARD_RCCL, SHARD_GROUP = 0, 1, 2  # prt_shard_info.transport
@@ -102,6 +103,11 @@ class DenoiseParams(C.Structure):
     """prt_denoise_params: iterations 1..8, normal_power 0..7 (log2 of the normal exponent), the three sigmas."""
     _fields_ = [("iterations", C.c_int32), ("normal_power", C.c_int32), ("sigma_color", C.c_float),
                 ("sigma_depth", C.c_float), ("sigma_albedo", C.c_float)]
+
+
+class ReprojectParams(C.Structure):
+    """prt_reproject_params: the relative depth tolerance, the least normal dot and the history cap (>= 1)."""
+    _fields_ = [("depth_tol", C.c_float), ("normal_min", C.c_float), ("max_history", C.c_float)]
 
 
 class ShardInfo(C.Structure):
@@ -178,6 +184,9 @@ def load():
         "prt_denoise_defaults": ([C.POINTER(DenoiseParams)], C.c_int),
         "prt_denoise": ([vp, C.POINTER(DenoiseParams), i32, i32, vp, vp, vp, vp, vp, u32], C.c_int),
         "prt_denoise_timings": ([vp, C.POINTER(C.c_float), i32], C.c_int),
+        "prt_reproject_defaults": ([C.POINTER(ReprojectParams)], C.c_int),
+        "prt_reproject": ([vp, C.POINTER(ReprojectParams), i32, i32, C.POINTER(CameraDesc), vp, vp,
+                           C.POINTER(CameraDesc), vp, vp, vp, vp, u32], C.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

@@ -93,6 +93,28 @@ def denoise_defaults(**overrides):
     return dp
 
 
+def reproject_defaults(**overrides):
+    """prt_reproject_params at the library's defaults (prt_reproject_defaults); keyword overrides set single fields
+    (depth_tol, normal_min, max_history)."""
+    rp = _lib.ReprojectParams()
+    check(_lib.load().prt_reproject_defaults(C.byref(rp)))
+    for k, v in overrides.items():
+        if k not in dict(rp._fields_):
+            raise TypeError(f"prt_reproject_params has no field {k!r}")
+        setattr(rp, k, v)
+    return rp
+
+
+def _camera_desc(cam):
+    """A Camera or a _lib.CameraDesc -> a copy of the prt_camera struct (the caller may go on moving its camera)."""
+    cd = _lib.CameraDesc()
+    C.memmove(C.byref(cd), C.byref(cam.desc if hasattr(cam, "desc") else cam), C.sizeof(cd))
+    return cd
+
+
+PANINI_REPROJECT = "temporal reprojection is defined for the plane projection only (isPostProcessed is set)"
+
+
 class Scene:
     """Scene (Core/Scene.h): models, BLAS instances (gameobject -> modelIndex + transform), lights, sky."""
 
@@ -361,6 +383,32 @@ class Context:
         check(self.L.prt_denoise_timings(self.h, ms, _lib.DENOISE_TIMINGS))
         return [float(v) for v in ms]
 
+    # -- temporal reprojection of the frame history (include/prt.h prt_reproject)
+    def reproject(self, color, normal_depth, camera, history=None, history_normal_depth=None, prev_camera=None, *,
+                  width, height, params=None, device_out=False, out=None, rgb8=None):
+        """`color` (render()'s avg of this frame) blended into the previous output `history` (rgb, w = history
+        length) reprojected from `prev_camera`'s view onto `camera`'s, guided by both views' render_aov()
+        normal_depth; returns (out[n,4], rgb8[n]), out's w the new history length.  history, history_normal_depth and
+        prev_camera are all None (a history starts) or all given.  Cameras: Camera or _lib.CameraDesc.  device_out:
+        every image is a raw device pointer, out / rgb8 are where the results go (either may be None; out may be
+        color, not a history buffer) and no host wait happens.  Plane projection only (no post-processing)."""
+        rp = params if params is not None else reproject_defaults()
+        n = width * height
+        cam = _camera_desc(camera)
+        prev = C.byref(_camera_desc(prev_camera)) if prev_camera is not None else None
+        if not device_out:
+            imgs = [_f32(a).reshape(n, 4) if a is not None else None
+                    for a in (color, normal_depth, history, history_normal_depth)]
+            out = np.zeros((n, 4), F32)
+            rgb8 = np.zeros(n, np.uint32)
+            pc, pn, ph, pg = (a.ctypes.data if a is not None else None for a in imgs)
+            po, p8 = out.ctypes.data, rgb8.ctypes.data
+        else:
+            pc, pn, ph, pg, po, p8 = color, normal_depth, history, history_normal_depth, out, rgb8
+        check(self.L.prt_reproject(self.h, C.byref(rp), width, height, C.byref(cam), pc, pn, prev, ph, pg, po, p8,
+                                   _lib.OUT_DEVICE if device_out else 0))
+        return out, rgb8
+
     def intersect(self, O, D, tmax=None):
         O, D = _f32(O), _f32(D)
         n = O.shape[0]
@@ -441,6 +489,7 @@ class Renderer:
         self.screen = np.zeros(width * height, np.uint32)
         self.average = np.zeros((width * height, 4), F32)
         self.last_stats = None
+        self._temporal = None  # TickTemporal's history: (width, height, out, normal_depth, camera)
         self.Init()
 
     def Init(self):
@@ -474,6 +523,33 @@ class Renderer:
         self.ctx.set_postfx(self.camera.postfx(self.isPostProcessed))  # the AOV primary rays follow Tick's (Panini)
         alb, nd = self.ctx.render_aov(self.width, self.height, flags)
         return self.ctx.denoise(self.average, alb, nd, self.width, self.height, params)
+
+    def TickTemporal(self, params=None):
+        """One Tick() that stands alone (the accumulation is reset in full first, and the camera handed over, so a
+        moved camera needs no CameraMoved()), reprojected onto the history this renderer keeps: the previous call's
+        output, AOVs and camera.  Returns (history, screen): float4 with the history length in w, and its 0x00RRGGBB
+        pixels (no screen pass).  self.average and self.screen are as Tick() left them.  The first call, a changed
+        image size or ResetTemporal() starts a new history.  Raises with isPostProcessed: Panini primary rays are
+        not described by the camera."""
+        if self.isPostProcessed:
+            raise ValueError(PANINI_REPROJECT)
+        W, H = self.width, self.height
+        self.ctx.set_camera(self.camera)
+        self.ctx.reset_accumulation(full=True)
+        self.Tick()
+        _, nd = self.ctx.render_aov(W, H, _lib.FLAG_NORMALMAP if self.NORMALMAPPED else 0)
+        cam = _camera_desc(self.camera)
+        t = self._temporal
+        if t is not None and t[:2] != (W, H):
+            t = None
+        hist, hist_nd, prev = t[2:] if t is not None else (None, None, None)
+        out, rgb8 = self.ctx.reproject(self.average, nd, cam, hist, hist_nd, prev, width=W, height=H, params=params)
+        self._temporal = (W, H, out, nd, cam)
+        return out, rgb8
+
+    def ResetTemporal(self):
+        """The next TickTemporal() starts a new history."""
+        self._temporal = None
 
     def Capture(self, path):
         """Renderer::Capture (Core/Renderer.cpp:437-465): the screen as a PNG (the reference names it by time)."""
