@@ -302,7 +302,11 @@ int prt_untile(prt_ctx* ctx, const float* gathered_device, int32_t width, int32_
 /* primary-ray closest hits for every pixel (config C2): out = W*H prt_hit (host or device per out_flags) */
 int prt_trace_primary(prt_ctx* ctx, int32_t width, int32_t height, prt_hit* hits, uint32_t out_flags,
                       prt_stats* stats);
-/* arbitrary rays: origins/dirs float3 x n (dirs normalised like the tinybvh::Ray ctor), tmax n (NULL = 1e30) */
+/* arbitrary rays: origins/dirs float3 x n (dirs normalised like the tinybvh::Ray ctor), tmax n (NULL = 1e30).
+ * prt_intersect: the closest hit with 0 < t < tmax (strict, as tinybvh's t < ray.hit.t: a triangle at exactly tmax
+ * is no hit, in whatever instance); among hits of equal t the smaller instance wins, then the larger prim.  A miss
+ * is the record t = tmax, u = v = 0, prim = inst = 0.
+ * prt_occluded: 1 when any triangle is hit with 0 < t < tmax (strict as well), else 0. */
 int prt_intersect(prt_ctx* ctx, int32_t n, const float* origins, const float* dirs, const float* tmax,
                   prt_hit* hits);
 int prt_occluded(prt_ctx* ctx, int32_t n, const float* origins, const float* dirs, const float* tmax,

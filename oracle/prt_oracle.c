@@ -1277,8 +1277,11 @@ int orc_intersect(orc_scene* s, int32_t n, const float* O, const float* D, const
 #pragma omp parallel for schedule(static)
     for (int i = 0; i < n; i++) {
         ray_t r = make_ray(v3(O[3 * i], O[3 * i + 1], O[3 * i + 2]), v3(D[3 * i], D[3 * i + 1], D[3 * i + 2]));
-        hit_t h; h.t = tmax ? tmax[i] : BVH_FAR; h.u = h.v = 0.0f; h.prim = 0; h.inst = 0;
+        /* a closest hit needs t < tmax (tinybvh's t < ray.hit.t): starting as (tmax, instance 0, prim ~0), no
+         * triangle at exactly tmax wins the tie in better(); a miss stays t = tmax, u = v = 0, prim = inst = 0 */
+        hit_t h; h.t = tmax ? tmax[i] : BVH_FAR; h.u = h.v = 0.0f; h.prim = 0xFFFFFFFFu; h.inst = 0;
         scene_closest(s, r.O, r.D, r.rD, &h);
+        if (h.prim == 0xFFFFFFFFu) h.prim = 0;
         t[i] = h.t; u[i] = h.u; v[i] = h.v; prim[i] = h.prim; inst[i] = h.inst;
     }
     return 0;

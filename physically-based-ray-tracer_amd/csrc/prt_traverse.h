@@ -8,7 +8,11 @@
 // t wins; an equal t goes to the smaller instance, then to the LARGER prim -- what BVH8_CPU's leaf does with
 // the two triangles of a quad sharing an edge (:6436 __bfind keeps the highest lane among equal minima, and
 // the leaves hold primitives in ascending order).  Box tests are conservative (inflated boxes, padded slab
-// interval), so the result does not depend on the BVH's shape.
+// interval), so the result does not depend on the BVH's shape.  The rule is written out in four places that must
+// agree (blas_traverse8's leaf update, the persistent kernels' leaf step and the cooperative tail's merge_team in
+// prt_persist.h, the oracle's better()); tests/test_gpu_degenerate.py pins it on inputs that tie on purpose
+// (duplicate triangles, coincident instances, rays through shared vertices), the oracle itself against a brute
+// force in tests/test_degenerate_ref.py.  A closest hit needs t < tmax (scene_closest8's initial state).
 //
 // Shared pieces of the traversal kernels: ray / hit records, the leaf test, the instance-box slab.
 #pragma once

@@ -223,19 +223,23 @@ __device__ __forceinline__ bool tlas_traverse8(const SceneDev& S, const Ray& r, 
 
 template <int STACK, int BLOCK>
 __device__ __forceinline__ Hit scene_closest8(const SceneDev& S, const Ray& r, float tmax, const LaneStack& stk) {
+  // a closest hit needs t < tmax: the walk starts as (tmax, instance 0, kNoPrim), which no triangle at exactly
+  // tmax beats under the tie rule (no instance is smaller, no prim larger); what is left of it is a miss
+  constexpr uint32_t kNoPrim = 0xFFFFFFFFu;
   Hit h;
-  h.t = tmax; h.u = 0.0f; h.v = 0.0f; h.prim = 0; h.inst = 0;
+  h.t = tmax; h.u = 0.0f; h.v = 0.0f; h.prim = kNoPrim; h.inst = 0;
   if (S.tlas) {
     (void)tlas_traverse8<STACK, BLOCK, false>(S, r, h, stk);
-    return h;
+  } else {
+    for (int i = 0; i < S.ninst; i++) {
+      const InstDev& I = S.inst[i];
+      if (slab1(I.bmin, I.bmax, r.O, r.rD, h.t) >= kFar) continue;
+      const V3 Oi = xform_point(r.O, I.inv), Di = xform_vector(r.D, I.inv);
+      const V3 rDi = v3(safercp(Di.x), safercp(Di.y), safercp(Di.z));
+      blas_traverse8<STACK, BLOCK, false>(S.nodes8, S.tris, S.mesh[I.mesh].root, Oi, Di, rDi, (uint32_t)i, h, stk);
+    }
   }
-  for (int i = 0; i < S.ninst; i++) {
-    const InstDev& I = S.inst[i];
-    if (slab1(I.bmin, I.bmax, r.O, r.rD, h.t) >= kFar) continue;
-    const V3 Oi = xform_point(r.O, I.inv), Di = xform_vector(r.D, I.inv);
-    const V3 rDi = v3(safercp(Di.x), safercp(Di.y), safercp(Di.z));
-    blas_traverse8<STACK, BLOCK, false>(S.nodes8, S.tris, S.mesh[I.mesh].root, Oi, Di, rDi, (uint32_t)i, h, stk);
-  }
+  if (h.prim == kNoPrim) h.prim = 0;  // the miss record: t = tmax, u = v = 0, prim = inst = 0
   return h;
 }
 

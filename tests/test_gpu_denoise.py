@@ -181,7 +181,8 @@ def test_device_pointers_and_aliasing(ctx, name):
             inplace, = _dev(stream, g["avg"])
             ctx.denoise(inplace.data_ptr(), alb_t.data_ptr(), nd_t.data_ptr(), W, H, par, device_out=True,
                         out=inplace.data_ptr())
-            only8 = torch.zeros_like(rgb_t)
+            with torch.cuda.stream(stream):  # zero-filled in the stream the filter writes it in, not beside it
+                only8 = torch.zeros_like(rgb_t)
             ctx.denoise(col_t.data_ptr(), alb_t.data_ptr(), nd_t.data_ptr(), W, H, par, device_out=True,
                         rgb8=only8.data_ptr())
             res[it] = (inplace, only8)
