@@ -238,6 +238,15 @@ int prt_reset_accumulation(prt_ctx* ctx, int32_t full);
  * the frames queued on the context's stream (a local group: on every member's, summed); reset != 0 zeroes the totals
  * after reading them. */
 int prt_ray_totals(prt_ctx* ctx, uint64_t* segments, uint64_t* shadow_rays, int32_t reset);
+/* Primary-hit reuse counters (additive within ABI 10).  Path 1 of a pixel starts at the pixel centre, so its
+ * primary ray is the same in every reference frame while camera, resolution, tile map, geometry and instances stay
+ * put; renders without extensions in render mode 0 trace it once per such state and reuse its hit (bit-identical
+ * images; PRT_PRIMARY_REUSE=0 in the environment traces every item's ray every frame).  traced: path-1 primary rays
+ * the calls so far handed to a traversal launch for reuse (one per pixel of the call's tile map); reused: those
+ * whose hit was taken from the kept records instead.  Both stay 0 where the reuse does not apply.  Host bookkeeping
+ * of the calls enqueued so far: no wait (a local group: summed over its members); reset != 0 zeroes them after
+ * reading.  A reused primary segment is still a segment of its path: prt_ray_totals and prt_stats count it. */
+int prt_primary_rays(prt_ctx* ctx, uint64_t* traced, uint64_t* reused, int32_t reset);
 
 /* ---- checkpoint / resume of the progressive accumulation (the reference keeps it in memory only) ----
  * The accumulation state Renderer holds between Ticks (Core/Renderer.h:61-63: accumulator, samplesPerPixel,

@@ -281,6 +281,10 @@ class Renderer {
   void RayTotals(uint64_t* segments, uint64_t* shadow_rays, bool reset = false) const {
     check(prt_ray_totals(ctx_, segments, shadow_rays, reset ? 1 : 0));
   }
+  // path-1 primary rays traced for reuse / taken from the kept records so far (prt_primary_rays; host counters)
+  void PrimaryRays(uint64_t* traced, uint64_t* reused, bool reset = false) const {
+    check(prt_primary_rays(ctx_, traced, reused, reset ? 1 : 0));
+  }
 
   // First-hit feature buffers of the scene and camera at pixel centres (prt_render_aov): albedo = base colour
   // (w = 1; miss 0), normal_depth = the shading normal as Trace uses it with the hit distance in w (miss

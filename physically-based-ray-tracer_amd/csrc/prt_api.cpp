@@ -84,11 +84,24 @@ hipError_t upload(DevBuf& b, const void* src, size_t n) {
 
 
 // wavefront state of one item group: the context's own (prt_ctx::ws), or of a concurrent group (prt_ctx::grp)
+// What the hit of a tile-map entry's path-1 primary ray (WaveBufs::phit) is a function of: the camera as the
+// kernels get it (SceneDev cam .. panini: the Panini post-process bends the primary rays), the resolution, the tile
+// map, and the epochs of the geometry and of the instance state (prt_ctx::scene_epoch / inst_epoch).  Zeroed before
+// it is filled (no padding), compared by its bytes.
+struct PrimKey {
+  float cam[12], basis[9], pan_b, pan_d;
+  int32_t panini, W, H, ts, rank, world;
+  uint64_t scene_epoch, inst_epoch;
+};
 struct WaveState {
   DevBuf wave;
   WaveBufs wb = {};
   uint32_t n = 0, levels = 0;
   bool ext = false, merge = false;
+  // primary-hit reuse: this state's own copy of the records and the key they were traced under (its stamp)
+  DevBuf phit;
+  PrimKey pkey = {};
+  bool pvalid = false;
 };
 // a frame in flight (prt_set_frames_in_flight): the wavefront chain of one call on its own stream.  Slot 0 uses the
 // context's own wavefront state and frame buffer, the others their own; done = the call's last work (the
@@ -312,6 +325,12 @@ struct prt_ctx {
   bool last_timers = false;
   uint64_t last_paths = 0;
   uint64_t carry_segments = 0, carry_shadow = 0;  // ray counts of a call's earlier frame passes
+  // primary-hit reuse (PrimKey): scene_epoch counts the calls that change geometry or BLASes (prt_set_meshes,
+  // prt_set_bvh_builder), inst_epoch those that change the instance records, the instance BVH or the hit word's
+  // encoding (prt_set_instances); prim_traced / prim_reused: path-1 primary rays handed to a dense pass / taken
+  // from phit by the calls so far (host bookkeeping, prt_primary_rays)
+  uint64_t scene_epoch = 0, inst_epoch = 0;
+  uint64_t prim_traced = 0, prim_reused = 0;
   // sharding (prt_shard_init_rccl / prt_shard_attach_rccl / prt_create_group)
   int32_t sh_kind = 0;  // 0 none, 1 RCCL, 2 local group (this context is member 0)
   int32_t sh_rank = 0, sh_world = 1, sh_tile = 32;
@@ -893,8 +912,29 @@ struct RenderPlan {
   int32_t F = 0, fmax = 1, npass = 1, F0 = 0;
   uint64_t per = 0;
   bool ext = false, merge = false;
+  bool preuse = false;  // primary-hit reuse applies to this call (primary_reuse_for)
   uint32_t iters = 0;
 };
+
+// Primary-hit reuse (prt_wave2.hip): the pipelines without extensions in render mode 0.  With an area light or
+// dielectrics the misses' pass rewrites hit[item] per item, and the debug modes shade from it: those keep tracing
+// P(0).  PRT_PRIMARY_REUSE=0 switches it off (every item's primary ray traced every frame; A/B runs, tests).
+bool primary_reuse_for(const prt_render_params* p, bool ext) {
+  const char* e = std::getenv("PRT_PRIMARY_REUSE");
+  return !ext && p->render_mode == 0 && p->bounces > 0 && !(e && std::atoi(e) == 0);
+}
+// the key of the primary hits a call with scene S and tile map M would trace
+PrimKey prim_key(const prt_ctx* c, const SceneDev& S, const TileMap& M) {
+  PrimKey k;
+  std::memset(&k, 0, sizeof(k));
+  std::memcpy(k.cam, S.cam, sizeof(k.cam));
+  std::memcpy(k.basis, S.basis, sizeof(k.basis));
+  k.pan_b = S.pan_b; k.pan_d = S.pan_d; k.panini = S.panini;
+  k.W = M.W; k.H = M.H; k.ts = M.ts; k.rank = M.rank; k.world = M.world;
+  k.scene_epoch = c->scene_epoch;
+  k.inst_epoch = c->inst_epoch;
+  return k;
+}
 
 // The merged pipeline (prt_wave2.hip k_shade2m): AA frames of render mode 0 without extensions, in calls small
 // enough that their traversal launches are bound by their slowest rays (one launch fewer per frame: world-8 share
@@ -953,6 +993,13 @@ int prepare_render(prt_ctx* c, const prt_render_params* p, const TileMap& M, int
   // sized for the first (largest) pass; later passes hold no more items
   rc = ensure_wave(flight_ws(c, fl), (uint32_t)(per * (uint64_t)F0), p->bounces, ext, merge);
   if (rc) return rc;
+  R.preuse = primary_reuse_for(p, ext) && per > 0 && F > 0;
+  if (R.preuse) {  // this chain's copy of the primary hits; a new allocation holds nothing yet
+    WaveState& ws = flight_ws(c, fl);
+    const void* before = ws.phit.p;
+    HIP_TRY(ws.phit.ensure(sizeof(float4) * (size_t)per));
+    if (ws.phit.p != before) ws.pvalid = false;
+  }
   R.F = F; R.fmax = fmax; R.npass = npass; R.F0 = F0; R.per = per; R.ext = ext; R.merge = merge; R.iters = iters;
   return PRT_OK;
 }
@@ -1023,6 +1070,27 @@ int enqueue_render_body(prt_ctx* c, const prt_render_params* p, const TileMap& M
     ws0.wb.base = 0;
     ws0.wb.coop_tail = coop;
     ws0.wb.tl = tl;
+    // primary-hit reuse: a stale stamp makes this pass's launch 0 the dense pass over its first frame (base is 0:
+    // items [0, per)), which fills this chain's phit; the later passes of the call and the later calls on this
+    // state reuse it until the key changes.  The stamp is set when the dense pass is enqueued: everything that
+    // reads phit afterwards follows it on this state's stream
+    ws0.wb.phit = ws0.phit.as<float4>();
+    ws0.wb.pitems = (uint32_t)per;
+    ws0.wb.pmode = kPrimTrace;
+    if (R.preuse && nb > 0) {
+      const PrimKey key = prim_key(c, S, M);
+      const uint64_t px = tile_image_pixels(M);  // the tile map's entries that have a pixel (and a ray)
+      if (ws0.pvalid && std::memcmp(&ws0.pkey, &key, sizeof(key)) == 0) {
+        ws0.wb.pmode = kPrimReuse;
+        c->prim_reused += px * (uint64_t)Fb;
+      } else {
+        ws0.wb.pmode = kPrimDense;
+        ws0.pkey = key;
+        ws0.pvalid = false;  // (until the pass is enqueued: a failed enqueue leaves the stamp stale)
+        c->prim_traced += px;
+        c->prim_reused += px * (uint64_t)(Fb - 1);
+      }
+    }
     {  // the queue counters and the fetch counters of the iterations this call uses (kMaxIters is the capacity)
       const size_t qw = (size_t)(iters + 2) * 2 * kNSub * kCtrStride;
       const size_t fbase = (size_t)(kMaxIters + 2) * 2 * kNSub * kCtrStride;
@@ -1033,6 +1101,7 @@ int enqueue_render_body(prt_ctx* c, const prt_render_params* p, const TileMap& M
     HIP_TRY(launch_wave_init(Lw, S, A, M, ws0.wb, frames));
     for (uint32_t it = 0; it <= iters; it++)
       HIP_TRY(launch_wave2_iter(Lw, S, A, M, ws0.wb, frames, timers ? &c->wt : nullptr, it));
+    if (ws0.wb.pmode == kPrimDense) ws0.pvalid = true;
     if (last && want_stats) HIP_TRY(hipEventRecord(c->ev[1], st));
     // post-processing (single-GPU image): the screen pass needs the average and, for the aberration, the
     // accumulator before the last frame
@@ -1549,6 +1618,7 @@ int prt_set_stream(prt_ctx* c, void* s) {
   const int rc = join_flights(c);  // the frames in flight complete in the old stream's order
   if (rc) return rc;
   c->stream = s ? reinterpret_cast<hipStream_t>(s) : c->own_stream;
+  c->ws.pvalid = false;  // the kept primary hits were written in the old stream's order: trace them again in the new
   return PRT_OK;
 }
 
@@ -1748,6 +1818,7 @@ int prt_set_meshes(prt_ctx* c, const prt_mesh* m_in, int32_t n) {
   c->max_depth = maxd;
   c->inst_dirty = true;
   c->tlas_dirty = true;
+  c->scene_epoch++;  // new geometry and BLASes (and prim bits of the hit word): kept primary hits are stale
   PRT_FOR_MEMBERS(prt_set_meshes(m, m_in, n));
   return PRT_OK;
 }
@@ -1756,6 +1827,7 @@ int prt_set_bvh_builder(prt_ctx* c, int32_t builder) {
   if (!c || builder < PRT_BUILDER_HOST_SAH || builder > PRT_BUILDER_GPU_PLOC)
     return fail(PRT_ERR_INVALID_ARGUMENT, "bad BLAS builder");
   c->builder = builder;
+  c->scene_epoch++;  // (the BLASes change at the next prt_set_meshes, which bumps it again)
   PRT_FOR_MEMBERS(prt_set_bvh_builder(m, builder));
   return PRT_OK;
 }
@@ -1769,6 +1841,7 @@ int prt_set_instances(prt_ctx* c, const float* xf, const uint32_t* mi, int32_t n
   c->inst_mesh.assign(mi, mi + n);
   c->inst_dirty = true;
   c->tlas_dirty = true;
+  c->inst_epoch++;  // transforms, boxes, the instance BVH and the hit word's instance bits: kept primary hits are stale
   HIP_TRY(hipSetDevice(c->device));
   if (!c->mesh_host.empty()) {
     const int rc = ensure_instances(c);
@@ -1789,6 +1862,9 @@ int prt_set_instance_materials(prt_ctx* c, const int32_t* kinds, int32_t n) {
       if (kinds[i] < PRT_MAT_TEXTURED || kinds[i] > PRT_MAT_MIRROR) return fail(PRT_ERR_INVALID_ARGUMENT, "bad material kind");
     c->inst_kind.assign(kinds, kinds + n);
   }
+  // No inst_epoch bump: a kept primary hit is (t, u, v, prim | inst << pbits), and a materials-only update moves no
+  // transform, box or tree (ensure_instances) and leaves pbits alone; the kind is read at shading, from the
+  // instance record.  Dielectric kinds switch to the extension kernels, which neither read nor write phit.
   c->inst_dirty = true;
   HIP_TRY(hipSetDevice(c->device));
   if (!c->mesh_host.empty() && !c->inst_mesh.empty()) {
@@ -1950,6 +2026,21 @@ int prt_ray_totals(prt_ctx* c, uint64_t* segments, uint64_t* shadow_rays, int32_
   HIP_TRY(hipSetDevice(c->device));
   *segments = seg;
   *shadow_rays = sh;
+  return PRT_OK;
+}
+
+int prt_primary_rays(prt_ctx* c, uint64_t* traced, uint64_t* reused, int32_t reset) {
+  if (!c || !traced || !reused) return fail(PRT_ERR_INVALID_ARGUMENT, "bad primary ray counter arguments");
+  // host bookkeeping of the calls enqueued so far (enqueue_render_body): no device counter, no wait
+  uint64_t t = c->prim_traced, r = c->prim_reused;
+  if (reset) c->prim_traced = c->prim_reused = 0;
+  for (prt_ctx* m : c->members) {
+    t += m->prim_traced;
+    r += m->prim_reused;
+    if (reset) m->prim_traced = m->prim_reused = 0;
+  }
+  *traced = t;
+  *reused = r;
   return PRT_OK;
 }
 

@@ -65,7 +65,15 @@ struct WaveBufs {
   float4* ro2;             // merge: the path-2 primary ray (k_wave_init), traced by k_trace2(0) ...
   float4* rd2;
   float4* hit2;            // ... into hit2; shaded by k_shade2 right after path 1 ends
+  // primary-hit reuse (prt_wave2.hip): the hit record of every tile-map entry's path-1 primary ray (the pixel
+  // centre: the same ray in every reference frame while camera, tile map, scene and instances stay put)
+  float4* phit;            // pitems records, entry r = (base + item) % pitems; one copy per wavefront state
+  uint32_t pitems;         // entries of the call's tile map (TileMap::items)
+  int32_t pmode;           // kPrimTrace: every item's primary ray is traced into hit (no reuse);
+                           // kPrimDense: launch 0 traces the pitems rays of the pass's first frame into phit;
+                           // kPrimReuse: phit is current, launch 0 traces no path-1 primary
 };
+enum : int32_t { kPrimTrace = 0, kPrimDense = 1, kPrimReuse = 2 };
 constexpr uint32_t kParts = 8;  // XCD parts of a traversal launch's live range, one fetch counter each (prt_queue.h)
 constexpr int kMaxIters = 128;  // wavefront iterations per call: bounces <= 64 (AA) / 6 with dielectrics (AA)
 #ifdef PRT_LANE_STATS

@@ -14,7 +14,8 @@
 //
 //   k_wave_init                                   P(0) = primary rays r1
 //   for i = 0 .. iters:
-//     k_trace2(i)    closest hits of P(i)  +  any hits of S(i-1)         (one launch, mixed lanes)
+//     k_trace2(i)    closest hits of P(i)  +  any hits of S(i-1)         (one launch, mixed lanes; P(0): the
+//                    primary-hit reuse below)
 //     k_res2d(i)     the items of P(i-1) (rinfo kRiFresh), walked in index order: NEE result of iteration i-1,
 //                    (result, throughput) stack, path end, frame write.  With the extensions or a debug render mode
 //                    k_resmiss2(i) walks the queue P(i-1) instead and also shades, for the items k_shade2(i-1)
@@ -26,6 +27,21 @@
 // S(i) reuses S(i-1)'s buffer after k_trace2(i) read it; the resolve (i) reads ne/nb/nk/vis/R/T of an item for
 // iteration i-1 before it (misses) or k_shade2(i) (hits) overwrites them; rinfo keeps iteration i-1's status
 // (and whether the item was queued) while info already holds the state of the queued next ray.
+//
+// Primary-hit reuse (plain and merged pipeline: no extensions, render mode 0; WaveBufs::phit / pmode).  Path 1 of
+// a pixel starts at the pixel centre (only path 2 is jittered, :61), so its primary ray is the same in every
+// reference frame of a call and in every later call while camera, tile map, scene and instances stay put.  Its
+// hit is kept in phit, one record per tile-map entry, and P(0) itself is never traced:
+//   kPrimDense  (the host's stamp of phit is stale) k_trace2(0) traces the entries of the pass's first frame in
+//               index order, once each, and writes phit; k_wave_init gave the padding entries a null ray
+//   kPrimReuse  (stamp current) k_trace2(0) traces only the merged pipeline's path-2 primaries; the plain
+//               pipeline does not launch it
+// and the shading of iteration 0 takes an item's hit from phit[(base + item) % pitems] instead of hit[item].
+// k_wave_init still queues every item into P(0) (the shading consumes it; the ray totals are the queue counters);
+// hit is written and read from iteration 1 on.  Writer of phit: k_trace2(0) of a dense pass; readers: the shading
+// kernels at iteration 0 of that pass and of every later pass and call on the same wavefront state.  Each state
+// (the context's own, one per further frame in flight) owns its copy and its stamp and runs its calls on one
+// stream at a time, so writer and readers are ordered by that stream and chains never share a copy.
 #include <cstdio>
 
 #include "prt_launch.h"
@@ -99,6 +115,12 @@ __global__ void __launch_bounds__(kBlock) k_wave_init(SceneDev S, TraceArgs A, T
         enq = true;
       } else {
         out[i] = make_float4(0.0f, 0.0f, 0.0f, kFar);  // bounces == 0: Trace returns 0, t1 stays BVH_FAR
+        // dense primary pass: a padding entry of the tile map (no pixel) holds the null ray (rd.w < 0), which
+        // k_trace2 turns into a query that ends at once and writes nothing
+        if (B.pmode == kPrimDense && gi < B.pitems) {
+          B.ro[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+          B.rd[i] = make_float4(0.0f, 0.0f, 1.0f, -1.0f);
+        }
         if (B.merge) B.rinfo[B.n + i] = 0u;
         B.rinfo[i] = 0u;
       }
@@ -140,14 +162,22 @@ __device__ __forceinline__ uint32_t shadow_vis(const WaveBufs& B, uint32_t code)
 }
 
 // ---- one traversal launch: closest hits of P(iter) (iter < iters) + any hits of S(iter - 1) (iter > 0)
-template <int REFILL, int STACK, int WAVES, int TAILN, bool TLAS, bool SPILL = false>
+// DENSE: the dense primary pass (iteration 0 of a pass with pmode kPrimDense), an instantiation of its own so
+// that the loop of every other launch carries no state for it
+template <int REFILL, int STACK, int WAVES, int TAILN, bool TLAS, bool SPILL = false, bool DENSE = false>
 __global__ void __launch_bounds__(64, WAVES) k_trace2(SceneDev S, WaveBufs B, uint32_t iter, uint32_t iters) {
   __shared__ uint32_t lds_stack[2 * STACK * 64];
   __shared__ uint32_t prefP[kNSub + 1], prefS[kNSub + 1];
   __shared__ uint32_t tail_lds[tail_lds_words(TAILN)];
   uint8_t* vis8 = reinterpret_cast<uint8_t*>(B.vis);
   const uint32_t* q = (iter & 1) ? B.q1 : B.q0;
-  const uint32_t nP = iter < iters ? load_prefix(B.ctr, iter, 0, prefP) : 0u;
+  // iteration 0 with primary-hit reuse: P(0) is not traced.  Dense pass: the first segment is the pitems entries
+  // of the pass's first frame in index order (slot g = item g = record g; base is 0), closest hits -> phit;
+  // kPrimReuse: phit is current and the segment is empty
+  constexpr bool dense = DENSE;
+  const uint32_t nP = DENSE ? B.pitems
+                            : (iter < iters && !(iter == 0 && B.pmode == kPrimReuse) ? load_prefix(B.ctr, iter, 0, prefP)
+                                                                                     : 0u);
   // merged pipeline, iteration 0: the second segment is the path-2 primaries (Q2, in shq; closest hits -> hit2)
   const bool q2 = iter == 0 && B.merge;
   const uint32_t nS = iter > 0 ? load_prefix(B.ctr, iter - 1, 1, prefS)
@@ -179,10 +209,11 @@ __global__ void __launch_bounds__(64, WAVES) k_trace2(SceneDev S, WaveBufs B, ui
         float4 o, d;
         uint32_t h;
         if (g < nP) {
-          h = q[map_slot(prefP, g, B.qcap)];
+          h = dense ? g : q[map_slot(prefP, g, B.qcap)];
           o = B.ro[h];
           d = B.rd[h];
-          tmax = kFar;
+          // (dense: k_wave_init's null ray of a padding entry; no box is entered at a negative limit)
+          tmax = (dense && d.w < 0.0f) ? -1.0f : kFar;
           any = false;
         } else if (q2) {  // a path-2 primary ray: handle = item | 1 << 31
           h = B.shq[map_slot(prefS, g - nP, B.scap)];
@@ -218,7 +249,8 @@ __global__ void __launch_bounds__(64, WAVES) k_trace2(SceneDev S, WaveBufs B, ui
         } else {
           const float4 rec = make_float4(hit.t, hit.u, hit.v, __uint_as_float(pack_hit(S, hit.prim, hit.inst)));
           if (h & 0x80000000u) B.hit2[h & 0x7FFFFFFFu] = rec;
-          else B.hit[h] = rec;
+          else if (!dense) B.hit[h] = rec;
+          else if (hit.t >= 0.0f) B.phit[h] = rec;  // (a padding entry's null query keeps t = -1)
         }
       },
       [&]() -> bool { return __hip_atomic_load(dflag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u; },
@@ -354,7 +386,8 @@ __global__ void __launch_bounds__(kBlock, EXT ? 3 : 1) k_shade2(SceneDev S, Trac
     if (gg < total) {
       item_n = q[map_slot(pref, gg, B.qcap)];
       info_n = B.info[item_n];
-      hh_n = B.hit[item_n];
+      // iteration 0 with primary-hit reuse (plain form only): the hit of the pixel's fixed path-1 primary ray
+      hh_n = (!EXT && iter == 0 && B.pmode != kPrimTrace) ? B.phit[(B.base + item_n) % B.pitems] : B.hit[item_n];
       seed_n = B.seed[item_n];
       if (!EXT) { ro_n = B.ro[item_n]; rd_n = B.rd[item_n]; }
     }
@@ -517,7 +550,8 @@ __global__ void __launch_bounds__(kBlock, 1) k_shade2m(SceneDev S, TraceArgs A, 
     if (gg < total) {
       item_n = q[map_slot(pref, gg, B.qcap)];
       info_n = B.info[item_n];
-      hh_n = B.hit[item_n];
+      // iteration 0 with primary-hit reuse: every item of P(0) is path 1 at depth 0, its hit is in phit
+      hh_n = (iter == 0 && B.pmode != kPrimTrace) ? B.phit[(B.base + item_n) % B.pitems] : B.hit[item_n];
       seed_n = B.seed[item_n];
     }
   };
@@ -816,30 +850,36 @@ __global__ void __launch_bounds__(kBlock) k_res2md(SceneDev S, TraceArgs A, Wave
 #ifndef PRT_REFILL
 #define PRT_REFILL 32  // idle lanes before a wave refills from the queue (A/B builds: -DPRT_REFILL=16 ...)
 #endif
-template <int STACK, int WAVES, int TAILN>
+template <int STACK, int WAVES, int TAILN, bool DENSE>
 void launch_t2(const LaunchCfg& c, const SceneDev& S, const WaveBufs& B, uint32_t it, uint32_t iters) {
   static_assert(2 * STACK * 256 + 264 + 4 * 3 * TAILN <= 163840 / (4 * WAVES), "LDS over the occupancy budget");
   if (S.tlas)
-    hipLaunchKernelGGL((k_trace2<PRT_REFILL, STACK, WAVES, TAILN, true>), dim3(256u * 4u * WAVES / c.groups), dim3(64), 0,
-                       c.stream, S, B, it, iters);
+    hipLaunchKernelGGL((k_trace2<PRT_REFILL, STACK, WAVES, TAILN, true, false, DENSE>),
+                       dim3(256u * 4u * WAVES / c.groups), dim3(64), 0, c.stream, S, B, it, iters);
   else
-    hipLaunchKernelGGL((k_trace2<PRT_REFILL, STACK, WAVES, TAILN, false>), dim3(256u * 4u * WAVES / c.groups), dim3(64), 0,
-                       c.stream, S, B, it, iters);
+    hipLaunchKernelGGL((k_trace2<PRT_REFILL, STACK, WAVES, TAILN, false, false, DENSE>),
+                       dim3(256u * 4u * WAVES / c.groups), dim3(64), 0, c.stream, S, B, it, iters);
 }
 // persistent traversal occupancy (waves/SIMD) -> LDS stack groups per lane; a BVH deeper than the 18 LDS
 // groups at 4 waves/SIMD hold runs the 4-wave form with the HBM spill columns (S.spill)
-static void launch_trace2(const LaunchCfg& c, const SceneDev& S, const WaveBufs& B, uint32_t it, uint32_t iters) {
+template <bool DENSE>
+static void launch_trace2_t(const LaunchCfg& c, const SceneDev& S, const WaveBufs& B, uint32_t it, uint32_t iters) {
   if (S.spill) {
     if (S.tlas)
-      hipLaunchKernelGGL((k_trace2<32, 18, 4, 32, true, true>), dim3(kSpillTraceBlocks / c.groups), dim3(64), 0,
+      hipLaunchKernelGGL((k_trace2<32, 18, 4, 32, true, true, DENSE>), dim3(kSpillTraceBlocks / c.groups), dim3(64), 0,
                          c.stream, S, B, it, iters);
     else
-      hipLaunchKernelGGL((k_trace2<32, 18, 4, 32, false, true>), dim3(kSpillTraceBlocks / c.groups), dim3(64), 0,
+      hipLaunchKernelGGL((k_trace2<32, 18, 4, 32, false, true, DENSE>), dim3(kSpillTraceBlocks / c.groups), dim3(64), 0,
                          c.stream, S, B, it, iters);
-  } else if (c.occ == 7) launch_t2<9, 7, 64>(c, S, B, it, iters);
-  else if (c.occ == 6) launch_t2<11, 6, 64>(c, S, B, it, iters);
-  else if (c.occ == 5) launch_t2<14, 5, 32>(c, S, B, it, iters);
-  else launch_t2<18, 4, 32>(c, S, B, it, iters);
+  } else if (c.occ == 7) launch_t2<9, 7, 64, DENSE>(c, S, B, it, iters);
+  else if (c.occ == 6) launch_t2<11, 6, 64, DENSE>(c, S, B, it, iters);
+  else if (c.occ == 5) launch_t2<14, 5, 32, DENSE>(c, S, B, it, iters);
+  else launch_t2<18, 4, 32, DENSE>(c, S, B, it, iters);
+}
+// (the dense primary pass of iteration 0 is an instantiation of its own, k_trace2)
+static void launch_trace2(const LaunchCfg& c, const SceneDev& S, const WaveBufs& B, uint32_t it, uint32_t iters) {
+  if (it == 0 && B.pmode == kPrimDense) launch_trace2_t<true>(c, S, B, it, iters);
+  else launch_trace2_t<false>(c, S, B, it, iters);
 }
 
 // producer grids (the kernels that append to the sub-queues: k_wave_init, the shading kernels): a multiple of kNSub,
@@ -868,7 +908,10 @@ hipError_t launch_wave2_iter(const LaunchCfg& c, const SceneDev& S, const TraceA
 #endif
   const uint32_t iters = wave_iters(S.has_diel != 0, A.bounces, A.flags, B.merge != 0);
   if (tm) (void)hipEventRecord(tm->ev[4 * it + 0], c.stream);
-  launch_trace2(c, S, B, it, iters);
+  // primary-hit reuse with a current phit: launch 0 of the plain pipeline has nothing to trace (no shadow rays yet,
+  // no path-2 primaries) and is not launched; its two timer events are still recorded, back to back (read_stats
+  // reads a pair per iteration; the launch shows as ~0 ms and leaves no PRT_DEBUG_QUEUES timeline record)
+  if (!(it == 0 && B.pmode == kPrimReuse && !B.merge)) launch_trace2(c, S, B, it, iters);
   if (tm) (void)hipEventRecord(tm->ev[4 * it + 1], c.stream);
   const bool ext = (S.area || S.has_diel) && A.mode == 0;
   // the misses' sky radiance: by k_shade2<false> itself, or (extensions: the area light can turn a hit into a miss

@@ -318,6 +318,15 @@ class Context:
         check(self.L.prt_ray_totals(self.h, C.byref(seg), C.byref(sh), 1 if reset else 0))
         return int(seg.value), int(sh.value)
 
+    def primary_rays(self, reset=False):
+        """(traced, reused): path-1 primary rays the calls so far traced for reuse (one per pixel of the call's
+        tile map, once per camera / tile map / scene / instance state and wavefront state) and those whose hit was
+        taken from the kept records instead (prt_primary_rays).  Host counters, no wait; both stay 0 where the
+        reuse does not apply (extensions, debug render modes, PRT_PRIMARY_REUSE=0)."""
+        tr, re_ = C.c_uint64(), C.c_uint64()
+        check(self.L.prt_primary_rays(self.h, C.byref(tr), C.byref(re_), 1 if reset else 0))
+        return int(tr.value), int(re_.value)
+
     def save_accumulation(self) -> bytes:
         """The accumulation state (accumulator, samplesPerPixel, distances) as an opaque blob
         (prt_save_accumulation); b"" before the first render."""
