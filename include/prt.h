@@ -247,6 +247,17 @@ int prt_ray_totals(prt_ctx* ctx, uint64_t* segments, uint64_t* shadow_rays, int3
  * of the calls enqueued so far: no wait (a local group: summed over its members); reset != 0 zeroes them after
  * reading.  A reused primary segment is still a segment of its path: prt_ray_totals and prt_stats count it. */
 int prt_primary_rays(prt_ctx* ctx, uint64_t* traced, uint64_t* reused, int32_t reset);
+/* Shadow-ray reuse counter (additive within ABI 10).  The next-event shadow rays of a pixel's fixed path-1 primary
+ * hit start at that hit and end at a light, so their answers repeat while the primary hits (above) and the positions
+ * of the point, directional and spot lights stay put.  Calls that reuse the primary hits record each answer the first
+ * time a frame traces it and skip the ray afterwards (bit-identical images; PRT_SHADOW_REUSE=0 in the environment
+ * switches only this off, PRT_PRIMARY_REUSE=0 both).  A call that traces the primary hits anew neither reads nor
+ * fills the record, so the skipping starts with the third call of a static view; new light positions clear the record
+ * but keep the primary hits, colours and materials keep both.  reused: the shadow rays answered from the record so
+ * far, counted on the device; waits for the frames queued on the context's stream like prt_ray_totals (a local group:
+ * summed over its members); reset != 0 zeroes it after reading.  A skipped shadow ray is still a shadow ray of its
+ * path: prt_ray_totals and prt_stats count it. */
+int prt_shadow_reuse(prt_ctx* ctx, uint64_t* reused, int32_t reset);
 
 /* ---- checkpoint / resume of the progressive accumulation (the reference keeps it in memory only) ----
  * The accumulation state Renderer holds between Ticks (Core/Renderer.h:61-63: accumulator, samplesPerPixel,

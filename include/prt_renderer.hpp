@@ -285,6 +285,12 @@ class Renderer {
   void PrimaryRays(uint64_t* traced, uint64_t* reused, bool reset = false) const {
     check(prt_primary_rays(ctx_, traced, reused, reset ? 1 : 0));
   }
+  // shadow rays answered from the kept light visibility of the primary hits so far (prt_shadow_reuse; waits)
+  uint64_t ShadowReuse(bool reset = false) const {
+    uint64_t reused = 0;
+    check(prt_shadow_reuse(ctx_, &reused, reset ? 1 : 0));
+    return reused;
+  }
 
   // First-hit feature buffers of the scene and camera at pixel centres (prt_render_aov): albedo = base colour
   // (w = 1; miss 0), normal_depth = the shading normal as Trace uses it with the hit distance in w (miss

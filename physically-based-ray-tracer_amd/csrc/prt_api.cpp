@@ -102,6 +102,13 @@ struct WaveState {
   DevBuf phit;
   PrimKey pkey = {};
   bool pvalid = false;
+  // light-visibility record (WaveBufs::lvis): valid for the phit it was learned on (pgen counts this state's
+  // dense passes, lgen is the count the record belongs to) and for the lights' positions (lpos: point,
+  // directional, spot; colours, the spot's direction and the flags shape no shadow ray)
+  DevBuf lvis;
+  uint64_t pgen = 0, lgen = 0;
+  float lpos[18] = {};
+  bool lvalid = false;
 };
 // a frame in flight (prt_set_frames_in_flight): the wavefront chain of one call on its own stream.  Slot 0 uses the
 // context's own wavefront state and frame buffer, the others their own; done = the call's last work (the
@@ -913,6 +920,7 @@ struct RenderPlan {
   uint64_t per = 0;
   bool ext = false, merge = false;
   bool preuse = false;  // primary-hit reuse applies to this call (primary_reuse_for)
+  bool lreuse = false;  // ... and the light-visibility record (shadow_reuse_on)
   uint32_t iters = 0;
 };
 
@@ -922,6 +930,12 @@ struct RenderPlan {
 bool primary_reuse_for(const prt_render_params* p, bool ext) {
   const char* e = std::getenv("PRT_PRIMARY_REUSE");
   return !ext && p->render_mode == 0 && p->bounces > 0 && !(e && std::atoi(e) == 0);
+}
+// The light-visibility record (prt_wave2.hip) rides on primary-hit reuse: wherever that applies, unless
+// PRT_SHADOW_REUSE=0 switches this alone off (A/B runs, tests)
+bool shadow_reuse_on() {
+  const char* e = std::getenv("PRT_SHADOW_REUSE");
+  return !(e && std::atoi(e) == 0);
 }
 // the key of the primary hits a call with scene S and tile map M would trace
 PrimKey prim_key(const prt_ctx* c, const SceneDev& S, const TileMap& M) {
@@ -999,6 +1013,12 @@ int prepare_render(prt_ctx* c, const prt_render_params* p, const TileMap& M, int
     const void* before = ws.phit.p;
     HIP_TRY(ws.phit.ensure(sizeof(float4) * (size_t)per));
     if (ws.phit.p != before) ws.pvalid = false;
+    R.lreuse = shadow_reuse_on();
+    if (R.lreuse) {  // and of the light-visibility record
+      const void* lbefore = ws.lvis.p;
+      HIP_TRY(ws.lvis.ensure(sizeof(uint2) * (size_t)per));
+      if (ws.lvis.p != lbefore) ws.lvalid = false;
+    }
   }
   R.F = F; R.fmax = fmax; R.npass = npass; R.F0 = F0; R.per = per; R.ext = ext; R.merge = merge; R.iters = iters;
   return PRT_OK;
@@ -1077,14 +1097,34 @@ int enqueue_render_body(prt_ctx* c, const prt_render_params* p, const TileMap& M
     ws0.wb.phit = ws0.phit.as<float4>();
     ws0.wb.pitems = (uint32_t)per;
     ws0.wb.pmode = kPrimTrace;
+    ws0.wb.lvis = nullptr;
+    ws0.wb.lslot = iters + 1;
     if (R.preuse && nb > 0) {
       const PrimKey key = prim_key(c, S, M);
       const uint64_t px = tile_image_pixels(M);  // the tile map's entries that have a pixel (and a ray)
       if (ws0.pvalid && std::memcmp(&ws0.pkey, &key, sizeof(key)) == 0) {
         ws0.wb.pmode = kPrimReuse;
         c->prim_reused += px * (uint64_t)Fb;
+        // the light-visibility record: used and filled by kPrimReuse passes only (a camera that moves every call
+        // pays nothing).  One learned on other primary hits (a dense pass since) or under other light positions
+        // is cleared, on this state's stream, before the pass reads it
+        if (R.lreuse) {
+          float lp[18];
+          std::memcpy(lp, S.ppos, sizeof(S.ppos));
+          std::memcpy(lp + 12, S.dpos, sizeof(S.dpos));
+          std::memcpy(lp + 15, S.spos, sizeof(S.spos));
+          if (!(ws0.lvalid && ws0.lgen == ws0.pgen && std::memcmp(lp, ws0.lpos, sizeof(lp)) == 0)) {
+            ws0.lvalid = false;
+            HIP_TRY(hipMemsetAsync(ws0.lvis.p, 0, sizeof(uint2) * (size_t)per, st));
+            ws0.lgen = ws0.pgen;
+            std::memcpy(ws0.lpos, lp, sizeof(lp));
+            ws0.lvalid = true;
+          }
+          ws0.wb.lvis = ws0.lvis.as<uint2>();
+        }
       } else {
         ws0.wb.pmode = kPrimDense;
+        ws0.pgen++;
         ws0.pkey = key;
         ws0.pvalid = false;  // (until the pass is enqueued: a failed enqueue leaves the stamp stale)
         c->prim_traced += px;
@@ -2041,6 +2081,26 @@ int prt_primary_rays(prt_ctx* c, uint64_t* traced, uint64_t* reused, int32_t res
   }
   *traced = t;
   *reused = r;
+  return PRT_OK;
+}
+
+int prt_shadow_reuse(prt_ctx* c, uint64_t* reused, int32_t reset) {
+  if (!c || !reused) return fail(PRT_ERR_INVALID_ARGUMENT, "bad shadow reuse counter arguments");
+  PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
+  std::vector<prt_ctx*> all{c};
+  all.insert(all.end(), c->members.begin(), c->members.end());
+  uint64_t n = 0;
+  for (prt_ctx* m : all) {  // the device's count (prt_wave2.hip lvis_total), 8 bytes behind the ray totals
+    HIP_TRY(hipSetDevice(m->device));
+    unsigned long long h = 0;
+    void* dev = ray_totals_dev(m) + 1;
+    HIP_TRY(hipMemcpyAsync(&h, dev, sizeof(h), hipMemcpyDeviceToHost, m->stream));
+    if (reset) HIP_TRY(hipMemsetAsync(dev, 0, sizeof(h), m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    n += h;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  *reused = n;
   return PRT_OK;
 }
 

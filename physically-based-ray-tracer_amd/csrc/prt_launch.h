@@ -72,6 +72,12 @@ struct WaveBufs {
   int32_t pmode;           // kPrimTrace: every item's primary ray is traced into hit (no reuse);
                            // kPrimDense: launch 0 traces the pitems rays of the pass's first frame into phit;
                            // kPrimReuse: phit is current, launch 0 traces no path-1 primary
+  // light-visibility record (prt_wave2.hip): per tile-map entry, indexed like phit, what the shadow rays from the
+  // entry's fixed primary hit towards the six light-class lights found (8 bytes: byte l for light l; 0 unknown,
+  // 1 occluded, 2 unoccluded).  Null unless the pass runs with kPrimReuse and the record belongs to phit and to
+  // the lights' positions (prt_api.cpp); one copy per wavefront state
+  uint2* lvis;
+  uint32_t lslot;          // the iteration whose shadow counter counts the rays answered from lvis (iters + 1)
 };
 enum : int32_t { kPrimTrace = 0, kPrimDense = 1, kPrimReuse = 2 };
 constexpr uint32_t kParts = 8;  // XCD parts of a traversal launch's live range, one fetch counter each (prt_queue.h)

@@ -10,6 +10,9 @@ constexpr uint32_t kRiQueued = 1u << 24;  // rinfo: the shading kernel queued th
 constexpr uint32_t kRiEmissive = 1u << 25;  // rinfo: a hit's emissive term is nonzero (stored in ne; else +0)
 constexpr uint32_t kRiFresh = 1u << 26;     // rinfo (merged pipeline): this slot was shaded in the last iteration
 
+// rinfo: iteration 0's shading queued shadow rays whose answers the resolve adds to the light-visibility record
+constexpr uint32_t kRiLearn = 1u << 27;
+
 __device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
 __device__ __forceinline__ uint32_t* qcounter(uint32_t* ctr, uint32_t iter, uint32_t which, uint32_t s) {
   return ctr + ((iter * 2u + which) * kNSub + s) * kCtrStride;
@@ -87,6 +90,36 @@ __device__ __forceinline__ uint32_t block_append(uint32_t* counter, uint32_t n, 
   __syncthreads();
   uint32_t off = sm[4];
   for (uint32_t k = 0; k < w; k++) off += sm[k];
+  __syncthreads();
+  return off + before;
+}
+
+// block_append that also counts, in the same two barriers, `skip` (0..4) entries per lane that are not appended:
+// the block's sum goes to `skipped` (a queue counter nothing prefixes) and to the running total `total`.  Blocks of
+// at most 4 waves (sm[0..3]: a wave's appended count in the low half, its skipped count in the high half).
+__device__ __forceinline__ uint32_t block_append_skip(uint32_t* counter, uint32_t n, uint32_t* skipped,
+                                                      unsigned long long* total, uint32_t skip, uint32_t* sm) {
+  const uint64_t b1 = __ballot(n & 1u), b2 = __ballot((n >> 1) & 1u), b4 = __ballot((n >> 2) & 1u);
+  const uint64_t k1 = __ballot(skip & 1u), k2 = __ballot((skip >> 1) & 1u), k4 = __ballot((skip >> 2) & 1u);
+  const uint64_t lt = (1ull << lane_id()) - 1ull;
+  const uint32_t before = (uint32_t)__popcll(b1 & lt) + 2u * (uint32_t)__popcll(b2 & lt) + 4u * (uint32_t)__popcll(b4 & lt);
+  const uint32_t wtot = (uint32_t)__popcll(b1) + 2u * (uint32_t)__popcll(b2) + 4u * (uint32_t)__popcll(b4);
+  const uint32_t wskip = (uint32_t)__popcll(k1) + 2u * (uint32_t)__popcll(k2) + 4u * (uint32_t)__popcll(k4);
+  const uint32_t w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  if (lane_id() == 0) sm[w] = wtot | (wskip << 16);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t tot = 0;
+    for (uint32_t k = 0; k < nw; k++) tot += sm[k];
+    sm[4] = (tot & 0xFFFFu) ? atomicAdd(counter, tot & 0xFFFFu) : 0u;
+    if (tot >> 16) {
+      atomicAdd(skipped, tot >> 16);
+      atomicAdd(total, (unsigned long long)(tot >> 16));
+    }
+  }
+  __syncthreads();
+  uint32_t off = sm[4];
+  for (uint32_t k = 0; k < w; k++) off += sm[k] & 0xFFFFu;
   __syncthreads();
   return off + before;
 }

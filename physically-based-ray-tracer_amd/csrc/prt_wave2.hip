@@ -42,6 +42,30 @@
 // kernels at iteration 0 of that pass and of every later pass and call on the same wavefront state.  Each state
 // (the context's own, one per further frame in flight) owns its copy and its stamp and runs its calls on one
 // stream at a time, so writer and readers are ordered by that stream and chains never share a copy.
+//
+// Light-visibility record (WaveBufs::lvis, next to phit and indexed like it; the same pipelines).  The shading of
+// iteration 0 builds every NEE shadow ray of path 1 from the fixed primary hit point and a light position alone
+// (light_ray); the RNG only picks which light class an item asks about.  So for a tile-map entry and a light the
+// any-hit answer of S(0) repeats while phit and the light positions stay put.  The record holds it: 8 bytes per
+// entry, byte l for light l (0-3 point, kLightDir, kLightSpot): 0 unknown, 1 occluded, 2 unoccluded.  Only passes
+// with pmode kPrimReuse use and fill it (B.lvis is null otherwise: a dense pass, or a camera that moves every call,
+// pays nothing), through instantiations of their own, so the kernels of every other launch are what they were:
+//   k_shade2<false, true> / k_shade2m<true> (iteration 0; the merged form's pass 0): reads the entry in the
+//               prefetch; queues, in compact slots, only the rays of the item's light class whose byte is 0; starts
+//               vis[item] with byte k = 1 for the rays known unoccluded; sets kRiLearn in rinfo if it queued any.
+//               nk, nb, hp and every RNG draw stay as they are.  The rays not queued are counted into the shadow
+//               counter of iteration iters + 1 (B.lslot), which no kernel prefixes and k_accumulate, read_stats and
+//               the multi-pass carry sum, so the ray totals still count every shadow ray the reference casts; and
+//               into the context's running total (prt_shadow_reuse)
+//   k_trace2(1) traces the shorter S(0); it is not changed
+//   k_res2d<true> / k_res2md<true> (launch 1; slot 0): for a kRiLearn item, writes what vis[item] now says into the
+//               bytes of the item's light class (lvis_learn)
+// There is no extra pass and no recomputed hit point: the record is learned from the very rays the frames trace.
+// Writer: the resolve of launch 1; reader: the shading of iteration 0 of a later pass or call on the same state (all
+// frames of a pass shade before its resolve runs, so a pass never reads what it writes).  Two frames of a pixel may
+// store the same bytes in one launch, always with the same values (the pattern of vis8).  Each wavefront state owns
+// its record; the host clears it (hipMemsetAsync on the state's stream, before k_wave_init) when a dense pass has
+// rewritten phit since it was learned or the light positions differ (prt_api.cpp enqueue_render_body).
 #include <cstdio>
 
 #include "prt_launch.h"
@@ -345,6 +369,33 @@ __device__ __forceinline__ bool diel_next(const WaveBufs& B, uint32_t item, uint
   return true;
 }
 
+// ---- the light-visibility record (WaveBufs::lvis; header comment).  An entry is 8 bytes, byte l for light l
+// (x: point lights 0-3, y: kLightDir, kLightSpot): 0 unknown, 1 occluded, 2 unoccluded.  Ray k of an item of
+// `kind` goes to light k (kind 0) or to the kind's one light (k = 0).
+static_assert(kBlock <= 256, "block_append_skip packs two counts of up to 4 x kBlock into one word");
+// the bytes of this kind's lights, ray k's in byte k -> ask: bit 8k set where ray k's answer is unknown (it is
+// queued); vis0: byte k = 1 where it is known unoccluded (the visibility word the traversal would have left)
+__device__ __forceinline__ void lvis_split(uint2 e, int kind, uint32_t& ask, uint32_t& vis0) {
+  const uint32_t w = kind == 0 ? e.x : ((kind == 2 ? e.y >> 8 : e.y) & 0xFFu);
+  const uint32_t rays = kind == 0 ? 0x01010101u : 1u;
+  vis0 = (w >> 1) & rays;
+  ask = ~(w | (w >> 1)) & rays;
+}
+// what the asked rays of a kRiLearn item found (its visibility word after the traversal; the bytes of rays that
+// were not asked hold what the record already said) -> the record.  Plain stores: every frame of a pixel that
+// learns writes the same values, and an item of kind 0 writes all four point-light bytes, as one word.
+__device__ __forceinline__ void lvis_learn(const WaveBufs& B, uint32_t item, uint32_t ri) {
+  const uint32_t kind = (ri >> 20) & 3u, vw = B.vis[item];
+  uint2* e = B.lvis + (B.base + item) % B.pitems;
+  if (kind == 0) e->x = 0x01010101u + (vw & 0x01010101u);
+  else reinterpret_cast<uint8_t*>(e)[kind == 2 ? 5 : 4] = (uint8_t)(1u + (vw & 1u));
+}
+// the context's running total of shadow rays answered from the record (prt_shadow_reuse): 8 bytes behind the ray
+// totals in the diagnostics buffer
+__device__ __forceinline__ unsigned long long* lvis_total(const SceneDev& S) {
+  return reinterpret_cast<unsigned long long*>(S.diag + 8);
+}
+
 // ---- shading of P(iter): NEE set-up -> S(iter), BRDF sample or path-2 start -> P(iter + 1)
 // k_shade2's parameter list as the kernarg segment holds it (explicit arguments in order, each at its natural
 // alignment, as C lays out these members)
@@ -359,8 +410,11 @@ typedef const __attribute__((address_space(4))) Shade2Args* Shade2ArgsPtr;
 // EXT (area light, dielectrics): held to 3 waves/SIMD (167 VGPRs, no spills; unbounded it takes 175 and runs 2
 // waves: C5 frame 135.7 -> 132.4 ms).  The plain form runs 4 waves at its natural 119 VGPRs (forcing 5 spilled
 // and was 2 % slower).
-template <bool EXT>
-__global__ void __launch_bounds__(kBlock, EXT ? 3 : 1) k_shade2(SceneDev S, TraceArgs A, TileMap M, WaveBufs B, uint32_t iter) {
+// I0 (plain form): iteration 0 of a pass with pmode kPrimReuse and a light-visibility record (B.lvis), an
+// instantiation of its own so that the shading of every other launch carries nothing for it
+template <bool EXT, bool I0 = false>
+__global__ void __launch_bounds__(kBlock, EXT ? 3 : (I0 ? 4 : 1)) k_shade2(SceneDev S, TraceArgs A, TileMap M, WaveBufs B, uint32_t iter) {
+  static_assert(!(EXT && I0), "the light-visibility record belongs to the plain pipelines");
   const Shade2ArgsPtr args = (Shade2ArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
   if (args->iter != iter || args->B.n != B.n) {  // the layout above does not match this compiler's: fail the call
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(S.diag + 1, 1u);
@@ -381,6 +435,7 @@ __global__ void __launch_bounds__(kBlock, EXT ? 3 : 1) k_shade2(SceneDev S, Trac
   uint32_t item_n = 0, info_n = 0, seed_n = 0;
   float4 hh_n = make_float4(kFar, 0.0f, 0.0f, 0.0f);
   float4 ro_n = make_float4(0.0f, 0.0f, 0.0f, 0.0f), rd_n = ro_n;  // (plain form: the ray too)
+  uint2 lv_n = make_uint2(0u, 0u);                                 // (I0: the entry's light-visibility bytes)
   auto prefetch = [&](uint32_t cc) {
     const uint32_t gg = cc * kBlock + threadIdx.x;
     if (gg < total) {
@@ -388,6 +443,7 @@ __global__ void __launch_bounds__(kBlock, EXT ? 3 : 1) k_shade2(SceneDev S, Trac
       info_n = B.info[item_n];
       // iteration 0 with primary-hit reuse (plain form only): the hit of the pixel's fixed path-1 primary ray
       hh_n = (!EXT && iter == 0 && B.pmode != kPrimTrace) ? B.phit[(B.base + item_n) % B.pitems] : B.hit[item_n];
+      if constexpr (I0) lv_n = B.lvis[(B.base + item_n) % B.pitems];
       seed_n = B.seed[item_n];
       if (!EXT) { ro_n = B.ro[item_n]; rd_n = B.rd[item_n]; }
     }
@@ -404,12 +460,14 @@ __global__ void __launch_bounds__(kBlock, EXT ? 3 : 1) k_shade2(SceneDev S, Trac
     const WaveBufs& Bc = *(const WaveBufs*)&ka->B;
     const uint32_t g = c * kBlock + threadIdx.x;
     uint32_t item = 0, info = 0, seed = 0, nr = 0;
+    uint32_t ask = 0, vis0 = 0;  // (I0) the rays to queue, bit 8k = ray k; the visibility word's initial value
     int kind = 0;
     float4 hh = make_float4(kFar, 0.0f, 0.0f, 0.0f);
     const bool active = g < total;
     if (active) {
       item = item_n; info = info_n; hh = hh_n;
       const uint32_t sd = seed_n;
+      const uint2 lv = lv_n;
       if ((info & 0x1FFu) == 0) Bc.s1[item].w = hh.x;                                        // r1.hit.t
       if (!EXT && hh.x >= kFar) {  // a miss (:159): the sky radiance (or 0) ends the path (EXT: k_miss2 / k_resmiss2)
         V3 L = v3(0.0f, 0.0f, 0.0f);
@@ -423,10 +481,15 @@ __global__ void __launch_bounds__(kBlock, EXT ? 3 : 1) k_shade2(SceneDev S, Trac
         seed = sd;
         kind = nee_kind(fl, seed);                                                           // :198-214
         nr = (uint32_t)nee_rays(kind);
+        if constexpr (I0) lvis_split(lv, kind, ask, vis0);
       }
     }
     prefetch(c + gridDim.x);
-    const uint32_t s0 = block_append(shcnt, nr, sm);  // the block's shadow-ray slots, one atomic
+    // the block's shadow-ray slots, one atomic (I0: of the rays whose answer is not known yet; the known ones are
+    // counted, not queued)
+    const uint32_t s0 = I0 ? block_append_skip(shcnt, (uint32_t)__popc(ask), qcounter(B.ctr, B.lslot, 1, sub),
+                                               lvis_total(S), nr - (uint32_t)__popc(ask), sm)
+                           : block_append(shcnt, nr, sm);
     const uint32_t depth = info & 0xFFu, path = (info >> 8) & 1u;
     uint32_t status = kStMiss, emissive = 0;
     bool next = false;
@@ -443,7 +506,12 @@ __global__ void __launch_bounds__(kBlock, EXT ? 3 : 1) k_shade2(SceneDev S, Trac
       Bc.hp[item] = make_float4(I.x, I.y, I.z, 0.0f);
       float4 nk;
       const V3 brdf = nee_lights(Sc, fl, kind, I, V, ha.N, ha.m, seed, nk, [&](int k, uint32_t light) {
-        shq[s0 + k] = (light << 29) | (4u * item + (uint32_t)k);
+        if constexpr (I0) {  // compact slots: the asked rays below k come first
+          if (ask & (1u << (8 * k)))
+            shq[s0 + (uint32_t)__popc(ask & ((1u << (8 * k)) - 1u))] = (light << 29) | (4u * item + (uint32_t)k);
+        } else {
+          shq[s0 + k] = (light << 29) | (4u * item + (uint32_t)k);
+        }
       });
       const V3 e = v3(0.0f, 0.0f, 0.0f) + v3(1.0f, 1.0f, 1.0f) * ha.m.emis;                // :196
       if (e.x != 0.0f || e.y != 0.0f || e.z != 0.0f) {  // otherwise e is +0 and the resolve rebuilds it
@@ -452,7 +520,7 @@ __global__ void __launch_bounds__(kBlock, EXT ? 3 : 1) k_shade2(SceneDev S, Trac
       }
       Bc.nb[item] = make_float4(brdf.x, brdf.y, brdf.z, 0.0f);
       Bc.nk[item] = nk;
-      Bc.vis[item] = 0u;
+      Bc.vis[item] = I0 ? vis0 : 0u;
       status = kStNeeEnd;
       if constexpr (EXT) {
         // area-light sample (2 draws after the light-class NEE draws) at lit, non-delta, non-dielectric hits
@@ -513,7 +581,7 @@ __global__ void __launch_bounds__(kBlock, EXT ? 3 : 1) k_shade2(SceneDev S, Trac
         if (!next) next = start_path2(Sc, A, M, Bc, item, path);
       }
       Bc.rinfo[item] = depth | (path << 8) | (status << 16) | ((uint32_t)kind << 20) | (next ? kRiQueued : 0u) | emissive |
-                       (EXT ? 0u : kResFresh);
+                       (EXT ? 0u : kResFresh) | ((I0 && ask) ? kRiLearn : 0u);
     }
     const uint32_t slot = block_append(ncnt, next ? 1u : 0u, sm);
     if (next) qn[sub * Bc.qcap + slot] = item;
@@ -526,7 +594,10 @@ __global__ void __launch_bounds__(kBlock, EXT ? 3 : 1) k_shade2(SceneDev S, Trac
 // k_trace2(0) traced next to path 1's: the RNG stream continues from path 1's last draw exactly as if path 2's
 // primary ray had been traced after path 1 ended, so the result is the same bit for bit and
 // a frame needs one wavefront iteration (a traversal, a shading and a resolve launch) fewer.
-__global__ void __launch_bounds__(kBlock, 1) k_shade2m(SceneDev S, TraceArgs A, TileMap M, WaveBufs B, uint32_t iter) {
+// I0: iteration 0 of a pass with pmode kPrimReuse and a light-visibility record, as k_shade2's; pass 0 of every
+// item is then path 1 at depth 0 (pass 1, path 2's first segment, asks for all its rays as ever)
+template <bool I0>
+__global__ void __launch_bounds__(kBlock, I0 ? 4 : 1) k_shade2m(SceneDev S, TraceArgs A, TileMap M, WaveBufs B, uint32_t iter) {
   const Shade2ArgsPtr args = (Shade2ArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
   if (args->iter != iter || args->B.n != B.n) {  // the Shade2Args layout does not match this compiler's: fail
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(S.diag + 1, 1u);
@@ -545,6 +616,7 @@ __global__ void __launch_bounds__(kBlock, 1) k_shade2m(SceneDev S, TraceArgs A, 
   const uint32_t levels = (uint32_t)max(1, A.bounces - 1);
   uint32_t item_n = 0, info_n = 0, seed_n = 0;
   float4 hh_n = make_float4(kFar, 0.0f, 0.0f, 0.0f);
+  uint2 lv_n = make_uint2(0u, 0u);
   auto prefetch = [&](uint32_t cc) {
     const uint32_t gg = cc * kBlock + threadIdx.x;
     if (gg < total) {
@@ -552,6 +624,7 @@ __global__ void __launch_bounds__(kBlock, 1) k_shade2m(SceneDev S, TraceArgs A, 
       info_n = B.info[item_n];
       // iteration 0 with primary-hit reuse: every item of P(0) is path 1 at depth 0, its hit is in phit
       hh_n = (iter == 0 && B.pmode != kPrimTrace) ? B.phit[(B.base + item_n) % B.pitems] : B.hit[item_n];
+      if constexpr (I0) lv_n = B.lvis[(B.base + item_n) % B.pitems];
       seed_n = B.seed[item_n];
     }
   };
@@ -566,6 +639,7 @@ __global__ void __launch_bounds__(kBlock, 1) k_shade2m(SceneDev S, TraceArgs A, 
     uint32_t item = 0, info = 0, seed = 0;
     float4 hh = make_float4(kFar, 0.0f, 0.0f, 0.0f);
     if (active) { item = item_n; info = info_n; hh = hh_n; seed = seed_n; }
+    const uint2 lv = lv_n;
     prefetch(c + gridDim.x);
     bool next = false, need2 = false;
 #pragma unroll 1
@@ -578,6 +652,8 @@ __global__ void __launch_bounds__(kBlock, 1) k_shade2m(SceneDev S, TraceArgs A, 
       const float4* rdp = pass ? Bc.rd2 : Bc.rd;
       int kind = 0;
       uint32_t nr = 0;
+      uint32_t ask = 0, vis0 = 0;  // (I0, pass 0) the rays to queue, bit 8k = ray k; the visibility word's start
+      const bool cached = I0 && pass == 0;
       if (act) {
         if ((info & 0x1FFu) == 0) Bc.s1[item].w = hh.x;                                     // r1.hit.t
         if (hh.x >= kFar) {  // a miss (:159): the sky radiance (or 0) ends the path
@@ -590,9 +666,13 @@ __global__ void __launch_bounds__(kBlock, 1) k_shade2m(SceneDev S, TraceArgs A, 
         } else {
           kind = nee_kind(fl, seed);                                                        // :198-214
           nr = (uint32_t)nee_rays(kind);
+          if (cached) lvis_split(lv, kind, ask, vis0);
         }
       }
-      const uint32_t s0 = block_append(shcnt, nr, sm);  // the block's shadow-ray slots, one atomic per pass
+      // the block's shadow-ray slots, one atomic per pass (I0, pass 0: of the rays not known yet, k_shade2)
+      const uint32_t s0 = cached ? block_append_skip(shcnt, (uint32_t)__popc(ask), qcounter(B.ctr, B.lslot, 1, sub),
+                                                     lvis_total(S), nr - (uint32_t)__popc(ask), sm)
+                                 : block_append(shcnt, nr, sm);
       uint32_t status = kStMiss, emissive = 0;
       if (nr) {
         const float4 o = rop[item], d = rdp[item];
@@ -604,7 +684,12 @@ __global__ void __launch_bounds__(kBlock, 1) k_shade2m(SceneDev S, TraceArgs A, 
         Bc.hp[sn] = make_float4(I.x, I.y, I.z, 0.0f);
         float4 nk;
         const V3 brdf = nee_lights(Sc, fl, kind, I, V, ha.N, ha.m, seed, nk, [&](int k, uint32_t light) {
-          shq[s0 + k] = (light << 29) | (4u * (uint32_t)sn + (uint32_t)k);
+          if (cached) {
+            if (ask & (1u << (8 * k)))
+              shq[s0 + (uint32_t)__popc(ask & ((1u << (8 * k)) - 1u))] = (light << 29) | (4u * (uint32_t)sn + (uint32_t)k);
+          } else {
+            shq[s0 + k] = (light << 29) | (4u * (uint32_t)sn + (uint32_t)k);
+          }
         });
         const V3 e = v3(0.0f, 0.0f, 0.0f) + v3(1.0f, 1.0f, 1.0f) * ha.m.emis;                // :196
         if (e.x != 0.0f || e.y != 0.0f || e.z != 0.0f) {
@@ -613,7 +698,7 @@ __global__ void __launch_bounds__(kBlock, 1) k_shade2m(SceneDev S, TraceArgs A, 
         }
         Bc.nb[sn] = make_float4(brdf.x, brdf.y, brdf.z, 0.0f);
         Bc.nk[sn] = nk;
-        Bc.vis[sn] = 0u;
+        Bc.vis[sn] = vis0;
         status = kStNeeEnd;
         if ((int)depth != A.bounces - 1) {                                                   // :329
           V3 dir, thr;
@@ -630,7 +715,8 @@ __global__ void __launch_bounds__(kBlock, 1) k_shade2m(SceneDev S, TraceArgs A, 
         Bc.seed[item] = seed;
       }
       if (act) {
-        Bc.rinfo[sn] = depth | (path << 8) | (status << 16) | ((uint32_t)kind << 20) | emissive | kRiFresh;
+        Bc.rinfo[sn] = depth | (path << 8) | (status << 16) | ((uint32_t)kind << 20) | emissive | kRiFresh |
+                       (ask ? kRiLearn : 0u);
         need2 = pass == 0 && path == 0 && status != kStNeeCont && (fl & kAA);
       }
     }
@@ -776,7 +862,10 @@ __global__ void __launch_bounds__(kBlock) k_resmiss2(SceneDev S, TraceArgs A, Wa
 }
 
 // dense resolve (plain pipeline, no extensions, render mode 0): every item in index order, the next item's rinfo
-// loaded while this one is resolved
+// loaded while this one is resolved.  LEARN: the resolve of launch 1 in a pass whose iteration 0 used the
+// light-visibility record (an instantiation of its own, like the shading's): it also records what the queued
+// shadow rays of the kRiLearn items found
+template <bool LEARN>
 __global__ void __launch_bounds__(kBlock) k_res2d(SceneDev S, TraceArgs A, WaveBufs B, float4* __restrict__ out) {
   const uint32_t stride = gridDim.x * kBlock;
   uint32_t item = blockIdx.x * kBlock + threadIdx.x;
@@ -786,7 +875,10 @@ __global__ void __launch_bounds__(kBlock) k_res2d(SceneDev S, TraceArgs A, WaveB
     if (item + stride < B.n) ri_n = B.rinfo[item + stride];
     if (!(ri & kRiFresh)) continue;
     resolve_item<false>(S, A, B, item, ri, out);
-    B.rinfo[item] = ri & ~kRiFresh;
+    if constexpr (LEARN) {
+      if (ri & kRiLearn) lvis_learn(B, item, ri);
+    }
+    B.rinfo[item] = ri & ~(kRiFresh | kRiLearn);
   }
 }
 
@@ -826,6 +918,7 @@ __device__ __forceinline__ void resolve_slot(const SceneDev& S, const TraceArgs&
     out[item] = make_float4(res.x, res.y, res.z, s1.w);
   }
 }
+template <bool LEARN>  // (as k_res2d's; slot 0 is path 1)
 __global__ void __launch_bounds__(kBlock) k_res2md(SceneDev S, TraceArgs A, WaveBufs B, float4* __restrict__ out) {
   const uint32_t stride = gridDim.x * kBlock;
   uint32_t item = blockIdx.x * kBlock + threadIdx.x;
@@ -836,7 +929,10 @@ __global__ void __launch_bounds__(kBlock) k_res2md(SceneDev S, TraceArgs A, Wave
     if (item + stride < B.n) { r0_n = B.rinfo[item + stride]; r1_n = B.rinfo[B.n + item + stride]; }
     if (r0 & kRiFresh) {
       resolve_slot(S, A, B, item, 0u, r0, out);
-      B.rinfo[item] = r0 & ~kRiFresh;
+      if constexpr (LEARN) {
+        if (r0 & kRiLearn) lvis_learn(B, item, r0);
+      }
+      B.rinfo[item] = r0 & ~(kRiFresh | kRiLearn);
     }
     if (r1 & kRiFresh) {
       resolve_slot(S, A, B, item, 1u, r1, out);
@@ -924,10 +1020,15 @@ hipError_t launch_wave2_iter(const LaunchCfg& c, const SceneDev& S, const TraceA
 #endif
   // the dense resolves over 2x the resident producer blocks (8 waves/SIMD), at most one chunk per block
   const unsigned gdense = std::min<unsigned>(2u * gprod, (B.n + kBlock - 1) / kBlock);
+  // iteration 0 of a kPrimReuse pass that holds a light-visibility record uses it (shading) and launch 1 adds to it
+  // (resolve): the instantiations of their own
+  const bool lrec = B.pmode == kPrimReuse && B.lvis != nullptr && !ext && A.mode == 0;
   if (it > 0 && B.merge) {
-    hipLaunchKernelGGL(k_res2md, dim3(gdense), dim3(kBlock), 0, c.stream, S, A, B, out);
+    if (lrec && it == 1) hipLaunchKernelGGL(k_res2md<true>, dim3(gdense), dim3(kBlock), 0, c.stream, S, A, B, out);
+    else hipLaunchKernelGGL(k_res2md<false>, dim3(gdense), dim3(kBlock), 0, c.stream, S, A, B, out);
   } else if (it > 0 && !ext && !sep_miss) {
-    hipLaunchKernelGGL(k_res2d, dim3(gdense), dim3(kBlock), 0, c.stream, S, A, B, out);
+    if (lrec && it == 1) hipLaunchKernelGGL(k_res2d<true>, dim3(gdense), dim3(kBlock), 0, c.stream, S, A, B, out);
+    else hipLaunchKernelGGL(k_res2d<false>, dim3(gdense), dim3(kBlock), 0, c.stream, S, A, B, out);
   } else if (it > 0) {  // resolve of P(it - 1) (+ misses of P(it)), one pass
     if (ext) hipLaunchKernelGGL(k_resmiss2<true>, dim3(gres), dim3(kBlock), 0, c.stream, S, A, B, it, iters, sep_miss,
                                 out);
@@ -938,9 +1039,12 @@ hipError_t launch_wave2_iter(const LaunchCfg& c, const SceneDev& S, const TraceA
     else hipLaunchKernelGGL(k_miss2<false>, dim3(gprod), dim3(kBlock), 0, c.stream, S, A, B, it);
   }
   if (it < iters) {
-    if (B.merge) hipLaunchKernelGGL(k_shade2m, dim3(gshade), dim3(kBlock), 0, c.stream, S, A, M, B, it);
+    const bool i0 = it == 0 && lrec;
+    if (B.merge && i0) hipLaunchKernelGGL(k_shade2m<true>, dim3(gshade), dim3(kBlock), 0, c.stream, S, A, M, B, it);
+    else if (B.merge) hipLaunchKernelGGL(k_shade2m<false>, dim3(gshade), dim3(kBlock), 0, c.stream, S, A, M, B, it);
     else if (A.mode != 0) hipLaunchKernelGGL(k_shade2_debug, dim3(gprod), dim3(kBlock), 0, c.stream, S, A, M, B, it);
     else if (ext) hipLaunchKernelGGL(k_shade2<true>, dim3(gshade), dim3(kBlock), 0, c.stream, S, A, M, B, it);
+    else if (i0) hipLaunchKernelGGL((k_shade2<false, true>), dim3(gshade), dim3(kBlock), 0, c.stream, S, A, M, B, it);
     else hipLaunchKernelGGL(k_shade2<false>, dim3(gshade), dim3(kBlock), 0, c.stream, S, A, M, B, it);
   }
   if (tm) tm->iters = iters + 1;

@@ -32,7 +32,7 @@ EXPORTS = [
     "prt_shard_attach_rccl", "prt_create_group", "prt_get_shard_info", "prt_accumulation_bytes",
     "prt_save_accumulation", "prt_load_accumulation", "prt_ray_totals", "prt_set_frames_in_flight", "prt_finish",
     "prt_render_aov", "prt_denoise_defaults", "prt_denoise", "prt_denoise_timings",
-    "prt_reproject_defaults", "prt_reproject", "prt_primary_rays",
+    "prt_reproject_defaults", "prt_reproject", "prt_primary_rays", "prt_shadow_reuse",
 ]
 SHARD_ID_BYTES = 128
 SHARD_NONE, SHARD_RCCL, SHARD_GROUP = 0, 1, 2  # prt_shard_info.transport
@@ -164,6 +164,7 @@ def load():
         "prt_load_accumulation": ([vp, vp, C.c_uint64], C.c_int),
         "prt_ray_totals": ([vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int32], C.c_int),
         "prt_primary_rays": ([vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int32], C.c_int),
+        "prt_shadow_reuse": ([vp, C.POINTER(C.c_uint64), C.c_int32], C.c_int),
         "prt_tile_buffer_pixels": ([i32, i32, i32, i32, C.POINTER(C.c_int64)], C.c_int),
         "prt_tile_pixel_map": ([i32, i32, i32, i32, i32, C.c_void_p], C.c_int),
         "prt_render_tiles": ([vp, C.POINTER(RenderParams), i32, i32, i32, vp, C.POINTER(Stats)], C.c_int),

@@ -244,6 +244,20 @@ class Context:
         else:
             check(L.prt_set_sky(self.h, None, 0, 0))
 
+    def set_lights(self, lt):
+        """The point, directional and spot lights alone (prt_set_lights) from a scenes.Lights; set_scene sets them
+        with the rest of the scene."""
+        l = _lib.Lights()
+        for i in range(4):
+            l.point_pos[i][:] = [float(v) for v in lt.point_pos[i]]
+            l.point_color[i][:] = [float(v) for v in lt.point_col[i]]
+        l.dir_pos[:] = [float(v) for v in lt.dir_pos]
+        l.dir_color[:] = [float(v) for v in lt.dir_col]
+        l.spot_pos[:] = [float(v) for v in lt.spot_pos]
+        l.spot_color[:] = [float(v) for v in lt.spot_col]
+        l.spot_rot[:] = [float(v) for v in lt.spot_rot]
+        check(self.L.prt_set_lights(self.h, C.byref(l)))
+
     def set_instances(self, blases):
         """Per-frame instance update (physics moved the game objects, Core/Renderer.cpp:33-41): the transforms
         go to the device and are refit there in stream order, so frames already queued keep the old ones."""
@@ -326,6 +340,15 @@ class Context:
         tr, re_ = C.c_uint64(), C.c_uint64()
         check(self.L.prt_primary_rays(self.h, C.byref(tr), C.byref(re_), 1 if reset else 0))
         return int(tr.value), int(re_.value)
+
+    def shadow_reuse(self, reset=False):
+        """Shadow rays of path-1 primary hits that the calls so far answered from the kept light visibility instead
+        of tracing them (prt_shadow_reuse).  Counted on the device: waits for the queued frames, like ray_totals.
+        0 where primary-hit reuse does not apply, with PRT_SHADOW_REUSE=0, and in the first two calls of a view (the
+        first traces the primary hits, the second learns)."""
+        n = C.c_uint64()
+        check(self.L.prt_shadow_reuse(self.h, C.byref(n), 1 if reset else 0))
+        return int(n.value)
 
     def save_accumulation(self) -> bytes:
         """The accumulation state (accumulator, samplesPerPixel, distances) as an opaque blob
