@@ -408,12 +408,63 @@ int prt_reproject_defaults(prt_reproject_params* out);
  * stages host images through context buffers, touches neither the accumulation state nor the ray totals, and on a
  * sharded or group context runs over the whole image on member 0's device.
  * Defined for the plane projection only: with Panini primary rays (post-processing on) the cameras do not describe
- * the rays, and this call cannot know -- the caller must not use it then (the Renderer mirrors refuse).  Moving
- * instances are not tracked: their pixels are rejected by the depth and normal tests, or ghost. */
+ * the rays, and this call cannot know -- the caller must not use it then (the Renderer mirrors refuse).  Only the
+ * camera moves here: a moving instance's pixels are rejected by the depth and normal tests, or ghost.
+ * prt_reproject_motion below follows the instances too. */
 int prt_reproject(prt_ctx* ctx, const prt_reproject_params* params, int32_t width, int32_t height,
                   const prt_camera* camera, const float* color_rgba, const float* normal_depth,
                   const prt_camera* prev_camera, const float* history_rgba, const float* history_normal_depth,
                   float* out_rgba, uint32_t* out_rgb8, uint32_t out_flags);
+
+/* ---- moving instances in the temporal reprojection (ABI 10, additive; DESIGN.md "Moving instances") ----
+ * The frame loop: prt_set_instances -> prt_render -> prt_render_aov_ids -> prt_instance_motion ->
+ * prt_reproject_motion -> prt_denoise. */
+
+/* (ABI 10, additive) prt_render_aov with one more output, from the same single primary-hit pass:
+ *   instance  uint32 W*H: the index of the first hit's instance, as prt_trace_primary reports it in prt_hit.inst;
+ *             a miss: 0xFFFFFFFF
+ * Everything else is prt_render_aov's contract: joins the frames in flight, runs on the context stream, any output
+ * may be NULL, host pointers unless PRT_OUT_DEVICE, PRT_OUT_TIMED times the whole pass (ms[0] of
+ * prt_denoise_timings). */
+int prt_render_aov_ids(prt_ctx* ctx, int32_t width, int32_t height, uint32_t flags,
+                       float* albedo_rgba, float* normal_depth, uint32_t* instance, uint32_t out_flags);
+
+/* (ABI 10, additive) host only, no context.  Per instance the motion matrix A = prev * inverse(cur), which carries a
+ * world-space point of this frame to where that point of the instance was in the previous frame.  transforms and
+ * prev_transforms are count row-major 4x4 matrices as prt_set_instances takes them, read as affine (the last row is
+ * ignored); motion receives count row-major 3x4 matrices (12 floats each), computed in double and rounded once.
+ * An instance whose 16 floats are bytewise equal in both arrays gets the exact identity (1,0,0,0, 0,1,0,0, 0,0,1,0).
+ * So does one whose current transform is non-finite or has determinant 0: such an instance covers no pixel, so its
+ * matrix is never read for a hit.  count 0 is allowed; a NULL array with count > 0 or a negative count is
+ * PRT_ERR_INVALID_ARGUMENT. */
+int prt_instance_motion(const float* transforms, const float* prev_transforms, int32_t count, float* motion);
+
+/* (ABI 10, additive) prt_reproject with the instances' motion taken into account.  With i = instance[p] and
+ * A = motion[i], the pixel's world-space hit X is carried back to X' = A * (X, 1) before it is projected into the
+ * previous view (the previous depth compared with the taps is |X' - prev pos|), the pixel's normal for the tap test
+ * is unit(A3x3 * N), and with history_instance given a tap q is kept only if history_instance[q] == i as well.
+ * A hit pixel with i >= count starts over and no matrix is read for it.  Everything else -- the operations, their
+ * order, the taps, the start-over rules, the outputs -- is prt_reproject's definition.  With identity matrices and
+ * history_instance NULL the output equals prt_reproject's bit for bit.
+ * The normal is transformed by A's 3x3 part itself, which is exact for rotations and uniform scales (what a physics
+ * engine produces) and approximate under non-uniform scale, where the inverse transpose would be needed.
+ *   instance              this view's prt_render_aov_ids buffer (required when there is a history)
+ *   history_instance      the previous view's, or NULL: taps are not compared by instance
+ *   motion, count         count 3x4 matrices (prt_instance_motion, or the caller's own): always a host array like the
+ *                         cameras, copied before the call returns and uploaded in the context stream's order
+ * Either prev_camera, history_rgba, history_normal_depth, history_instance and motion are all NULL and count is 0 (a
+ * history starts: out = (color.rgb, 1)), or prev_camera, history_rgba, history_normal_depth and motion are all given
+ * with count > 0 (history_instance stays optional); anything else is PRT_ERR_INVALID_ARGUMENT, and so is an out_rgba
+ * that is history_rgba or history_normal_depth, or an out_rgb8 that is history_instance.  out_rgba may be color_rgba.
+ * Image pointers all host, or all device with PRT_OUT_DEVICE (then the call does not wait on the host).  What
+ * prt_reproject says about frames in flight, sharded contexts, side effects and Panini holds here too.
+ * Not tracked: lighting that changes because an object moved (its shadow on a static surface lags by up to
+ * max_history frames), deforming meshes. */
+int prt_reproject_motion(prt_ctx* ctx, const prt_reproject_params* params, int32_t width, int32_t height,
+                         const prt_camera* camera, const float* color_rgba, const float* normal_depth,
+                         const uint32_t* instance, const prt_camera* prev_camera, const float* history_rgba,
+                         const float* history_normal_depth, const uint32_t* history_instance, const float* motion,
+                         int32_t count, float* out_rgba, uint32_t* out_rgb8, uint32_t out_flags);
 
 /* ---- shading-function probe (ABI 10): the device's own BRDF functions (the ones the shading kernels inline) on
  * n host records, for known-answer tests of the BRDF restatement (Core/BRDF.cpp).  Record k: in[24 k ..], out[8 k ..].

@@ -351,10 +351,54 @@ class Renderer {
                         out.data(), screen8.data(), 0u));
     hist_ = out;
     hist_nd_.swap(normal_depth);
+    hist_ids_.clear();  // (a following TickTemporalMotion() starts a new history)
     hist_cam_ = cam;
     history.swap(out);
   }
-  void ResetTemporal() { hist_.clear(); }  // the next TickTemporal() starts a new history
+  // TickTemporal() that follows moving instances (prt_reproject_motion): scene.gameobjects is handed to the context
+  // first (Scene::UploadInstances), the first hits' instance ids are rendered with the AOVs (prt_render_aov_ids), the
+  // previous ids and transforms are kept with the history, and the motion matrices come from prt_instance_motion.  A
+  // changed instance count starts a new history, and so does a call that follows a plain TickTemporal().
+  void TickTemporalMotion(std::vector<float>& history, std::vector<uint32_t>& screen8,
+                          const prt_reproject_params& params = ReprojectDefaults()) {
+    if (isPostProcessed)
+      throw Error(PRT_ERR_INVALID_ARGUMENT,
+                  "temporal reprojection is defined for the plane projection only (isPostProcessed is set)");
+    scene.UploadInstances(ctx_);
+    const prt_camera cam = camera.Plane();
+    check(prt_set_camera(ctx_, &cam));
+    check(prt_reset_accumulation(ctx_, 1));
+    Tick();
+    const size_t n = (size_t)width_ * height_;
+    std::vector<float> normal_depth(4 * n, 0.0f), out(4 * n, 0.0f), xf;
+    std::vector<uint32_t> ids(n, 0u);
+    check(prt_render_aov_ids(ctx_, width_, height_, NORMALMAPPED ? PRT_FLAG_NORMALMAP : 0u, nullptr,
+                             normal_depth.data(), ids.data(), 0u));
+    for (const GameObject& g : scene.gameobjects) xf.insert(xf.end(), g.transform.begin(), g.transform.end());
+    screen8.assign(n, 0u);
+    const int32_t count = (int32_t)scene.gameobjects.size();
+    if (hist_.empty() || hist_ids_.empty() || hist_xf_.size() != xf.size() || count == 0) {
+      check(prt_reproject_motion(ctx_, &params, width_, height_, &cam, accumulator.data(), normal_depth.data(),
+                                 ids.data(), nullptr, nullptr, nullptr, nullptr, nullptr, 0, out.data(),
+                                 screen8.data(), 0u));
+    } else {
+      std::vector<float> motion(12 * (size_t)count);
+      check(prt_instance_motion(xf.data(), hist_xf_.data(), count, motion.data()));
+      check(prt_reproject_motion(ctx_, &params, width_, height_, &cam, accumulator.data(), normal_depth.data(),
+                                 ids.data(), &hist_cam_, hist_.data(), hist_nd_.data(), hist_ids_.data(),
+                                 motion.data(), count, out.data(), screen8.data(), 0u));
+    }
+    hist_ = out;
+    hist_nd_.swap(normal_depth);
+    hist_ids_.swap(ids);
+    hist_xf_.swap(xf);
+    hist_cam_ = cam;
+    history.swap(out);
+  }
+  void ResetTemporal() {  // the next TickTemporal() / TickTemporalMotion() starts a new history
+    hist_.clear();
+    hist_ids_.clear();
+  }
 
   uint32_t Flags() const {
     return (AA ? PRT_FLAG_AA : 0u) | (accumulates ? PRT_FLAG_ACCUMULATE : 0u) | (GAMMACORRECTED ? PRT_FLAG_GAMMA : 0u) |
@@ -373,6 +417,8 @@ class Renderer {
   prt_stats stats_{};
   std::vector<float> hist_, hist_nd_;  // TickTemporal's history: previous output, previous normal_depth (empty: none)
   prt_camera hist_cam_{};              // ... and the camera they were made with
+  std::vector<uint32_t> hist_ids_;     // TickTemporalMotion's: the previous instance ids (empty: no such history)
+  std::vector<float> hist_xf_;         // ... and the previous instance transforms (16 floats each)
 };
 
 }  // namespace prt

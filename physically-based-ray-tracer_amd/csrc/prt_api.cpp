@@ -22,6 +22,7 @@
 #include "bvh_gpu.h"
 #include "prt_denoise.h"
 #include "prt_launch.h"
+#include "prt_motion.h"
 #include "prt_rccl.h"
 #include "prt_refit.h"
 #include "prt_temporal.h"
@@ -360,6 +361,9 @@ struct prt_ctx {
   int32_t dn_timed_aov = 0, dn_timed_passes = 0;   // what the last timed calls recorded
   // temporal reprojection (prt_reproject): staging of host images (colour, normal_depth, history, its normal_depth)
   DevBuf rp_in[4], rp_out, rp_rgb8;
+  // instance ids and motion (prt_render_aov_ids / prt_reproject_motion): the id output's staging, the staging of host
+  // id images (this view's, the previous view's) and the motion matrices on the device
+  DevBuf aov_ids, rp_ids[2], rp_motion;
 };
 
 namespace {
@@ -2348,8 +2352,10 @@ int dn_event(prt_ctx* c, int k) {  // record timing event k on the context strea
 bool sigma_ok(float v, bool zero_ok) { return std::isfinite(v) && (zero_ok ? v >= 0.0f : v > 0.0f); }
 }  // namespace
 
-int prt_render_aov(prt_ctx* c, int32_t W, int32_t H, uint32_t flags, float* albedo, float* normal_depth,
-                   uint32_t out_flags) {
+namespace {
+// prt_render_aov / prt_render_aov_ids: one primary-hit pass, then k_aov and / or k_aov_ids over its hits
+int render_aov(prt_ctx* c, int32_t W, int32_t H, uint32_t flags, float* albedo, float* normal_depth,
+               uint32_t* instance, uint32_t out_flags) {
   if (!c || W <= 0 || H <= 0 || W > 16384 || H > 16384) return fail(PRT_ERR_INVALID_ARGUMENT, "bad AOV arguments");
   PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
   HIP_TRY(hipSetDevice(c->device));
@@ -2358,7 +2364,7 @@ int prt_render_aov(prt_ctx* c, int32_t W, int32_t H, uint32_t flags, float* albe
   if (rc) return rc;
   if (!c->have_camera) return fail(PRT_ERR_NOT_READY, "no camera");
   if (!depth_ok(c)) return fail(PRT_ERR_UNSUPPORTED, "BVH deeper than 64 levels");
-  if (!albedo && !normal_depth) return PRT_OK;
+  if (!albedo && !normal_depth && !instance) return PRT_OK;
   const TileMap M = make_tilemap(W, H, 8, 0, 1);
   const size_t n = (size_t)W * H;
   rc = ensure_spill(c, S, (size_t)M.items + 256);
@@ -2368,14 +2374,18 @@ int prt_render_aov(prt_ctx* c, int32_t W, int32_t H, uint32_t flags, float* albe
   HIP_TRY(c->counters.ensure(sizeof(Counters)));  // the launch's own ray count: not the running totals
   float4* a = reinterpret_cast<float4*>(albedo);
   float4* g = reinterpret_cast<float4*>(normal_depth);
+  uint32_t* ids = instance;
   if (!dev_out) {
     if (albedo) { HIP_TRY(c->aov_alb.ensure(n * sizeof(float4))); a = c->aov_alb.as<float4>(); }
     if (normal_depth) { HIP_TRY(c->aov_nd.ensure(n * sizeof(float4))); g = c->aov_nd.as<float4>(); }
+    if (instance) { HIP_TRY(c->aov_ids.ensure(n * 4)); ids = c->aov_ids.as<uint32_t>(); }
   }
   LaunchCfg L{c->stream, occ_for(c)};
   if (timed && (rc = dn_event(c, 0))) return rc;
   HIP_TRY(launch_primary_hits(L, S, M, c->aov_hits.as<HitOut>(), c->counters.as<Counters>()));
-  HIP_TRY(launch_aov(c->stream, S, W, H, (flags & PRT_FLAG_NORMALMAP) != 0, c->aov_hits.as<HitOut>(), a, g));
+  if (a || g)
+    HIP_TRY(launch_aov(c->stream, S, W, H, (flags & PRT_FLAG_NORMALMAP) != 0, c->aov_hits.as<HitOut>(), a, g));
+  if (ids) HIP_TRY(launch_aov_ids(c->stream, W, H, c->aov_hits.as<HitOut>(), ids));
   if (timed) {
     if ((rc = dn_event(c, 1))) return rc;
     c->dn_timed_aov = 1;
@@ -2383,9 +2393,20 @@ int prt_render_aov(prt_ctx* c, int32_t W, int32_t H, uint32_t flags, float* albe
   if (!dev_out) {
     if (albedo) HIP_TRY(hipMemcpyAsync(albedo, a, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     if (normal_depth) HIP_TRY(hipMemcpyAsync(normal_depth, g, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    if (instance) HIP_TRY(hipMemcpyAsync(instance, ids, n * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
   }
   return PRT_OK;
+}
+}  // namespace
+
+int prt_render_aov(prt_ctx* c, int32_t W, int32_t H, uint32_t flags, float* albedo, float* normal_depth,
+                   uint32_t out_flags) {
+  return render_aov(c, W, H, flags, albedo, normal_depth, nullptr, out_flags);
+}
+int prt_render_aov_ids(prt_ctx* c, int32_t W, int32_t H, uint32_t flags, float* albedo, float* normal_depth,
+                       uint32_t* instance, uint32_t out_flags) {
+  return render_aov(c, W, H, flags, albedo, normal_depth, instance, out_flags);
 }
 
 int prt_denoise_defaults(prt_denoise_params* out) {
@@ -2536,6 +2557,128 @@ int prt_reproject(prt_ctx* c, const prt_reproject_params* p, int32_t W, int32_t 
   P.out = dst;
   P.rgb8 = dst8;
   HIP_TRY(launch_reproject(c->stream, P));
+  if (!dev) {
+    if (out_rgba) HIP_TRY(hipMemcpyAsync(out_rgba, dst, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (out_rgb8) HIP_TRY(hipMemcpyAsync(out_rgb8, dst8, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  return PRT_OK;
+}
+
+// ---- moving instances in the temporal reprojection (prt_motion.hip)
+int prt_instance_motion(const float* transforms, const float* prev_transforms, int32_t count, float* motion) {
+  if (count < 0 || (count > 0 && (!transforms || !prev_transforms || !motion)))
+    return fail(PRT_ERR_INVALID_ARGUMENT, "bad instance motion arguments");
+  static const float kIdentity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+  for (int32_t k = 0; k < count; k++) {
+    const float* T = transforms + 16 * (size_t)k;
+    const float* Q = prev_transforms + 16 * (size_t)k;
+    float* A = motion + 12 * (size_t)k;
+    std::memcpy(A, kIdentity, sizeof(kIdentity));
+    if (std::memcmp(T, Q, 16 * sizeof(float)) == 0) continue;  // at rest: the exact identity
+    double m[3][3], t[3];
+    bool finite = true;
+    for (int r = 0; r < 3; r++) {
+      for (int j = 0; j < 3; j++) m[r][j] = T[4 * r + j];
+      t[r] = T[4 * r + 3];
+      for (int j = 0; j < 4; j++) finite = finite && std::isfinite(T[4 * r + j]);
+    }
+    const double c00 = m[1][1] * m[2][2] - m[1][2] * m[2][1], c01 = m[1][2] * m[2][0] - m[1][0] * m[2][2],
+                 c02 = m[1][0] * m[2][1] - m[1][1] * m[2][0];
+    const double det = m[0][0] * c00 + m[0][1] * c01 + m[0][2] * c02;
+    if (!finite || det == 0.0 || !std::isfinite(1.0 / det)) continue;  // no visible pixel: identity
+    const double id = 1.0 / det;
+    const double inv[3][3] = {
+        {c00 * id, (m[0][2] * m[2][1] - m[0][1] * m[2][2]) * id, (m[0][1] * m[1][2] - m[0][2] * m[1][1]) * id},
+        {c01 * id, (m[0][0] * m[2][2] - m[0][2] * m[2][0]) * id, (m[0][2] * m[1][0] - m[0][0] * m[1][2]) * id},
+        {c02 * id, (m[0][1] * m[2][0] - m[0][0] * m[2][1]) * id, (m[0][0] * m[1][1] - m[0][1] * m[1][0]) * id}};
+    for (int r = 0; r < 3; r++) {  // A = [Mp * inv, tp - Mp * inv * t]
+      double row[3], tr = Q[4 * r + 3];
+      for (int j = 0; j < 3; j++) {
+        row[j] = ((double)Q[4 * r] * inv[0][j] + (double)Q[4 * r + 1] * inv[1][j]) + (double)Q[4 * r + 2] * inv[2][j];
+        tr -= row[j] * t[j];
+      }
+      for (int j = 0; j < 3; j++) A[4 * r + j] = (float)row[j];
+      A[4 * r + 3] = (float)tr;
+    }
+  }
+  return PRT_OK;
+}
+
+int prt_reproject_motion(prt_ctx* c, const prt_reproject_params* p, int32_t W, int32_t H, const prt_camera* cam,
+                         const float* color, const float* normal_depth, const uint32_t* instance,
+                         const prt_camera* prev_cam, const float* history, const float* history_nd,
+                         const uint32_t* history_inst, const float* motion, int32_t count, float* out_rgba,
+                         uint32_t* out_rgb8, uint32_t out_flags) {
+  if (!c || !p || !cam || !color || !normal_depth || (!out_rgba && !out_rgb8) || W <= 0 || H <= 0 || W > 16384 ||
+      H > 16384)
+    return fail(PRT_ERR_INVALID_ARGUMENT, "bad reproject arguments");
+  if (!sigma_ok(p->depth_tol, true) || !(p->normal_min >= -1.0f && p->normal_min <= 1.0f) ||
+      !std::isfinite(p->max_history) || p->max_history < 1.0f)
+    return fail(PRT_ERR_INVALID_ARGUMENT, "reproject parameters out of range");
+  const int given = (prev_cam ? 1 : 0) + (history ? 1 : 0) + (history_nd ? 1 : 0) + (motion ? 1 : 0) + (count ? 1 : 0);
+  if (count < 0 || (given != 0 && given != 5) || (given == 0 && history_inst))
+    return fail(PRT_ERR_INVALID_ARGUMENT,
+                "prev_camera, history_rgba, history_normal_depth, motion and count > 0 go together");
+  if (given && !instance) return fail(PRT_ERR_INVALID_ARGUMENT, "instance is NULL with a history");
+  if (out_rgba && given && (out_rgba == history || out_rgba == history_nd))
+    return fail(PRT_ERR_INVALID_ARGUMENT, "out_rgba must not be a history buffer");
+  if (out_rgb8 && history_inst && out_rgb8 == history_inst)
+    return fail(PRT_ERR_INVALID_ARGUMENT, "out_rgb8 must not be history_instance");
+  PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t n = (size_t)W * H, bytes = n * sizeof(float4);
+  const bool dev = (out_flags & PRT_OUT_DEVICE) != 0;
+  const float4* src[4] = {reinterpret_cast<const float4*>(color), reinterpret_cast<const float4*>(normal_depth),
+                          reinterpret_cast<const float4*>(history), reinterpret_cast<const float4*>(history_nd)};
+  const uint32_t* ids[2] = {given ? instance : nullptr, history_inst};
+  float4* dst = reinterpret_cast<float4*>(out_rgba);
+  uint32_t* dst8 = out_rgb8;
+  if (!dev) {  // host images: staged in context buffers
+    for (int k = 0; k < 4; k++) {
+      if (!src[k]) continue;
+      HIP_TRY(c->rp_in[k].ensure(bytes));
+      HIP_TRY(hipMemcpyAsync(c->rp_in[k].p, src[k], bytes, hipMemcpyHostToDevice, c->stream));
+      src[k] = c->rp_in[k].as<float4>();
+    }
+    for (int k = 0; k < 2; k++) {
+      if (!ids[k]) continue;
+      HIP_TRY(c->rp_ids[k].ensure(n * 4));
+      HIP_TRY(hipMemcpyAsync(c->rp_ids[k].p, ids[k], n * 4, hipMemcpyHostToDevice, c->stream));
+      ids[k] = c->rp_ids[k].as<uint32_t>();
+    }
+    if (out_rgba) { HIP_TRY(c->rp_out.ensure(bytes)); dst = c->rp_out.as<float4>(); }
+    if (out_rgb8) { HIP_TRY(c->rp_rgb8.ensure(n * 4)); dst8 = c->rp_rgb8.as<uint32_t>(); }
+  }
+  if (given) {  // the matrices: copied into a pinned staging buffer now, uploaded in stream order (no host wait)
+    const size_t mb = 12 * sizeof(float) * (size_t)count;
+    HIP_TRY(c->rp_motion.ensure(mb));
+    StageSlot* st = nullptr;
+    const int rc = stage_acquire(c, mb, st);
+    if (rc) return rc;
+    std::memcpy(st->p, motion, mb);
+    HIP_TRY(hipMemcpyAsync(c->rp_motion.p, st->p, mb, hipMemcpyHostToDevice, c->stream));
+    const int rr = stage_release(c, *st, c->stream);
+    if (rr) return rr;
+  }
+  MotionPass P{};
+  P.R.W = W;
+  P.R.H = H;
+  P.R.depth_tol = p->depth_tol;
+  P.R.normal_min = p->normal_min;
+  P.R.max_history = p->max_history;
+  make_reproject_pass(P.R, *cam, prev_cam);
+  P.R.color = src[0];
+  P.R.nd = src[1];
+  P.R.hist = src[2];
+  P.R.hist_nd = src[3];
+  P.R.out = dst;
+  P.R.rgb8 = dst8;
+  P.inst = ids[0];
+  P.hist_inst = ids[1];
+  P.motion = given ? c->rp_motion.as<float4>() : nullptr;
+  P.count = count;
+  HIP_TRY(launch_reproject_motion(c->stream, P));
   if (!dev) {
     if (out_rgba) HIP_TRY(hipMemcpyAsync(out_rgba, dst, bytes, hipMemcpyDeviceToHost, c->stream));
     if (out_rgb8) HIP_TRY(hipMemcpyAsync(out_rgb8, dst8, n * 4, hipMemcpyDeviceToHost, c->stream));

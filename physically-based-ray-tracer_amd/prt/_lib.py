@@ -33,6 +33,7 @@ EXPORTS = [
     "prt_save_accumulation", "prt_load_accumulation", "prt_ray_totals", "prt_set_frames_in_flight", "prt_finish",
     "prt_render_aov", "prt_denoise_defaults", "prt_denoise", "prt_denoise_timings",
     "prt_reproject_defaults", "prt_reproject", "prt_primary_rays", "prt_shadow_reuse",
+    "prt_render_aov_ids", "prt_instance_motion", "prt_reproject_motion",
 ]
 SHARD_ID_BYTES = 128
 SHARD_NONE, SHARD_RCCL, SHARD_GROUP = 0, 1, 2  # prt_shard_info.transport
@@ -189,6 +190,10 @@ def load():
         "prt_reproject_defaults": ([C.POINTER(ReprojectParams)], C.c_int),
         "prt_reproject": ([vp, C.POINTER(ReprojectParams), i32, i32, C.POINTER(CameraDesc), vp, vp,
                            C.POINTER(CameraDesc), vp, vp, vp, vp, u32], C.c_int),
+        "prt_render_aov_ids": ([vp, i32, i32, u32, vp, vp, vp, u32], C.c_int),
+        "prt_instance_motion": ([vp, vp, i32, vp], C.c_int),
+        "prt_reproject_motion": ([vp, C.POINTER(ReprojectParams), i32, i32, C.POINTER(CameraDesc), vp, vp, vp,
+                                  C.POINTER(CameraDesc), vp, vp, vp, vp, i32, vp, vp, u32], C.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

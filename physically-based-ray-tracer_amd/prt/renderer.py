@@ -112,6 +112,17 @@ def _camera_desc(cam):
     return cd
 
 
+def instance_motion(transforms, prev_transforms):
+    """prt_instance_motion: the [count, 12] float32 motion matrices prev * inverse(cur) of two sets of row-major 4x4
+    instance transforms (anything that reshapes to [count, 16]); host only, no context."""
+    cur, prev = _f32(transforms).reshape(-1, 16), _f32(prev_transforms).reshape(-1, 16)
+    if cur.shape != prev.shape:
+        raise ValueError("instance_motion: the two sets of transforms differ in count")
+    out = np.zeros((len(cur), 12), F32)
+    check(_lib.load().prt_instance_motion(cur.ctypes.data, prev.ctypes.data, len(cur), out.ctypes.data))
+    return out
+
+
 PANINI_REPROJECT = "temporal reprojection is defined for the plane projection only (isPostProcessed is set)"
 
 
@@ -441,6 +452,53 @@ class Context:
                                    _lib.OUT_DEVICE if device_out else 0))
         return out, rgb8
 
+    # -- moving instances in the reprojection (include/prt.h prt_render_aov_ids / prt_reproject_motion)
+    def render_aov_ids(self, width, height, flags=_lib.FLAG_NORMALMAP, device_out=False, albedo=None,
+                       normal_depth=None, instance=None, timed=False):
+        """render_aov() with the first hit's instance index per pixel (uint32, a miss 0xFFFFFFFF) from the same
+        primary-hit pass: (albedo[n,4], normal_depth[n,4], instance[n]).  device_out: the three are raw device
+        pointers (any may be None)."""
+        n = width * height
+        if not device_out:
+            albedo = np.zeros((n, 4), F32)
+            normal_depth = np.zeros((n, 4), F32)
+            instance = np.zeros(n, np.uint32)
+            pa, pn, pi = albedo.ctypes.data, normal_depth.ctypes.data, instance.ctypes.data
+        else:
+            pa, pn, pi = albedo, normal_depth, instance
+        of = (_lib.OUT_DEVICE if device_out else 0) | (_lib.OUT_TIMED if timed else 0)
+        check(self.L.prt_render_aov_ids(self.h, width, height, flags, pa, pn, pi, of))
+        return albedo, normal_depth, instance
+
+    def reproject_motion(self, color, normal_depth, instance, camera, history=None, history_normal_depth=None,
+                         prev_camera=None, history_instance=None, motion=None, *, width, height, params=None,
+                         device_out=False, out=None, rgb8=None):
+        """reproject() that follows moving instances: `instance` / `history_instance` are both views'
+        render_aov_ids() ids and `motion` the [count, 12] matrices of instance_motion() (always a host array).
+        history, history_normal_depth, prev_camera and motion are all None (a history starts) or all given;
+        history_instance is optional (None: taps are not compared by instance).  Returns (out[n,4], rgb8[n])."""
+        rp = params if params is not None else reproject_defaults()
+        n = width * height
+        cam = _camera_desc(camera)
+        prev = C.byref(_camera_desc(prev_camera)) if prev_camera is not None else None
+        mo = _f32(motion).reshape(-1, 12) if motion is not None else None
+        pm, count = (mo.ctypes.data, len(mo)) if mo is not None else (None, 0)
+        if not device_out:
+            imgs = [_f32(a).reshape(n, 4) if a is not None else None
+                    for a in (color, normal_depth, history, history_normal_depth)]
+            ids = [np.ascontiguousarray(a, np.uint32).reshape(n) if a is not None else None
+                   for a in (instance, history_instance)]
+            out = np.zeros((n, 4), F32)
+            rgb8 = np.zeros(n, np.uint32)
+            pc, pn, ph, pg, pi, pj = (a.ctypes.data if a is not None else None for a in imgs + ids)
+            po, p8 = out.ctypes.data, rgb8.ctypes.data
+        else:
+            pc, pn, ph, pg, pi, pj, po, p8 = (color, normal_depth, history, history_normal_depth, instance,
+                                              history_instance, out, rgb8)
+        check(self.L.prt_reproject_motion(self.h, C.byref(rp), width, height, C.byref(cam), pc, pn, pi, prev, ph, pg,
+                                          pj, pm, count, po, p8, _lib.OUT_DEVICE if device_out else 0))
+        return out, rgb8
+
     def intersect(self, O, D, tmax=None):
         O, D = _f32(O), _f32(D)
         n = O.shape[0]
@@ -521,7 +579,7 @@ class Renderer:
         self.screen = np.zeros(width * height, np.uint32)
         self.average = np.zeros((width * height, 4), F32)
         self.last_stats = None
-        self._temporal = None  # TickTemporal's history: (width, height, out, normal_depth, camera)
+        self._temporal = None  # TickTemporal's history: (width, height, out, normal_depth, camera[, ids, transforms])
         self.Init()
 
     def Init(self):
@@ -556,16 +614,22 @@ class Renderer:
         alb, nd = self.ctx.render_aov(self.width, self.height, flags)
         return self.ctx.denoise(self.average, alb, nd, self.width, self.height, params)
 
-    def TickTemporal(self, params=None):
+    def TickTemporal(self, params=None, motion=False):
         """One Tick() that stands alone (the accumulation is reset in full first, and the camera handed over, so a
         moved camera needs no CameraMoved()), reprojected onto the history this renderer keeps: the previous call's
         output, AOVs and camera.  Returns (history, screen): float4 with the history length in w, and its 0x00RRGGBB
         pixels (no screen pass).  self.average and self.screen are as Tick() left them.  The first call, a changed
         image size or ResetTemporal() starts a new history.  Raises with isPostProcessed: Panini primary rays are
-        not described by the camera."""
+        not described by the camera.
+        motion=True follows moving instances: scene.blases is handed to the context first (set_instances), the
+        instance ids are rendered with the AOVs, the previous ids and transforms are kept with the history, and the
+        pass is reproject_motion with the matrices of instance_motion; a changed instance count starts a new history,
+        and so does a call that follows one with motion=False (which kept no ids)."""
         if self.isPostProcessed:
             raise ValueError(PANINI_REPROJECT)
         W, H = self.width, self.height
+        if motion:
+            return self._tick_temporal_motion(params, W, H)
         self.ctx.set_camera(self.camera)
         self.ctx.reset_accumulation(full=True)
         self.Tick()
@@ -574,9 +638,29 @@ class Renderer:
         t = self._temporal
         if t is not None and t[:2] != (W, H):
             t = None
-        hist, hist_nd, prev = t[2:] if t is not None else (None, None, None)
+        hist, hist_nd, prev = t[2:5] if t is not None else (None, None, None)
         out, rgb8 = self.ctx.reproject(self.average, nd, cam, hist, hist_nd, prev, width=W, height=H, params=params)
         self._temporal = (W, H, out, nd, cam)
+        return out, rgb8
+
+    def _tick_temporal_motion(self, params, W, H):
+        self.ctx.set_instances(self.scene.blases)
+        self.ctx.set_camera(self.camera)
+        self.ctx.reset_accumulation(full=True)
+        self.Tick()
+        _, nd, ids = self.ctx.render_aov_ids(W, H, _lib.FLAG_NORMALMAP if self.NORMALMAPPED else 0)
+        cam = _camera_desc(self.camera)
+        xf = _f32(np.stack([T for _, T in self.scene.blases])).reshape(-1, 16).copy()
+        t = self._temporal
+        if t is not None and (t[:2] != (W, H) or len(t) != 7 or len(t[6]) != len(xf)):
+            t = None
+        if t is None:
+            out, rgb8 = self.ctx.reproject_motion(self.average, nd, ids, cam, width=W, height=H, params=params)
+        else:
+            hist, hist_nd, prev, hist_ids, prev_xf = t[2:]
+            out, rgb8 = self.ctx.reproject_motion(self.average, nd, ids, cam, hist, hist_nd, prev, hist_ids,
+                                                  instance_motion(xf, prev_xf), width=W, height=H, params=params)
+        self._temporal = (W, H, out, nd, cam, ids, xf)
         return out, rgb8
 
     def ResetTemporal(self):
