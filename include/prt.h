@@ -459,12 +459,87 @@ int prt_instance_motion(const float* transforms, const float* prev_transforms, i
  * Image pointers all host, or all device with PRT_OUT_DEVICE (then the call does not wait on the host).  What
  * prt_reproject says about frames in flight, sharded contexts, side effects and Panini holds here too.
  * Not tracked: lighting that changes because an object moved (its shadow on a static surface lags by up to
- * max_history frames), deforming meshes. */
+ * max_history frames; prt_reproject_moments' clamp_k below shortens that), deforming meshes. */
 int prt_reproject_motion(prt_ctx* ctx, const prt_reproject_params* params, int32_t width, int32_t height,
                          const prt_camera* camera, const float* color_rgba, const float* normal_depth,
                          const uint32_t* instance, const prt_camera* prev_camera, const float* history_rgba,
                          const float* history_normal_depth, const uint32_t* history_instance, const float* motion,
                          int32_t count, float* out_rgba, uint32_t* out_rgb8, uint32_t out_flags);
+
+/* ---- luminance moments and the variance-guided filter (ABI 10, additive; DESIGN.md "Variance guidance") ----
+ * The frame loop: prt_set_instances -> prt_render -> prt_render_aov_ids -> prt_instance_motion ->
+ * prt_reproject_moments -> prt_denoise_variance; out_rgba and out_moments (not the filtered image) are the next
+ * frame's history. */
+typedef struct {
+  float depth_tol, normal_min, max_history; /* as prt_reproject_params: same defaults (0.05, 0.9, 16), same ranges */
+  float clamp_k;      /* 0 = no clamp (default); > 0: the gathered history is clamped per channel to
+                         mean +- clamp_k * sigma of this frame's 3x3 neighbourhood; finite, >= 0 */
+  float min_temporal; /* history length from which the variance comes from the moments; finite, >= 1, default 4 */
+} prt_temporal_params;
+
+/* host only, no context */
+int prt_temporal_defaults(prt_temporal_params* out);
+
+/* (ABI 10, additive) prt_reproject_motion that also carries the first two moments of the luminance
+ * L(c) = (0.2126 c.x + 0.7152 c.y) + 0.0722 c.z with the history and estimates its variance.
+ *   moments images   float4 per pixel: x = first moment, y = second moment, z = the variance estimate
+ *                    prt_denoise_variance reads, w = 0
+ * A pixel with history (k_reproject_motion's rules decide, with the same taps q, weights wb, sum ws, length len and
+ * a = 1 / len): hm1 = (sum wb * M_q.x) / ws and hm2 likewise over the kept taps in the colour gather's order; with
+ * clamp_k > 0 the gathered colour h is clamped per channel to [mu - k sigma, mu + k sigma], where over the in-image
+ * pixels of the 3x3 neighbourhood of p in color_rgba (row-major, n of them) mu = (sum c) / n and
+ * sigma = sqrt(max((sum c * c) / n - mu * mu, 0)); then the colour blends as in prt_reproject_motion,
+ * m1 = hm1 + a * (L - hm1), m2 = hm2 + a * (L * L - hm2).  A pixel that starts over (no history given, a miss, an id
+ * >= count, behind or off the previous screen, ws <= 1/64) has out = (color.rgb, 1), m1 = L, m2 = L * L, len = 1.
+ * The variance: 0 for a miss; max(m2 - m1 * m1, 0) when len >= min_temporal; otherwise the spatial estimate
+ * max(s2 / n - mu * mu, 0) * (min_temporal / len) with s1 = sum L_q, s2 = sum L_q * L_q, mu = s1 / n over the pixels q
+ * of the 5x5 window of p (row-major, inside the image) that are hits (normal_depth.w < 1e30) with
+ * instance[q] == instance[p].
+ * With clamp_k == 0 out_rgba and out_rgb8 equal prt_reproject_motion's bit for bit.
+ * Arguments as prt_reproject_motion, except:
+ *   instance         always required (the 5x5 window compares ids even when a history starts)
+ *   history_moments  the previous call's out_moments: given with prev_camera, history_rgba, history_normal_depth and
+ *                    motion (count > 0), or NULL with all of them (history_instance stays optional)
+ *   out_moments      required; must not be history_moments
+ *   out_rgba         must not be color_rgba: unlike prt_reproject_motion this pass reads the neighbours of color_rgba
+ *                    (the clamp's 3x3 and the variance's 5x5 window), which another thread may already have overwritten
+ * Anything else is PRT_ERR_INVALID_ARGUMENT.  Host / device pointers, frames in flight, the stream, sharded contexts,
+ * side effects and Panini: as prt_reproject_motion. */
+int prt_reproject_moments(prt_ctx* ctx, const prt_temporal_params* params, int32_t width, int32_t height,
+                          const prt_camera* camera, const float* color_rgba, const float* normal_depth,
+                          const uint32_t* instance, const prt_camera* prev_camera, const float* history_rgba,
+                          const float* history_normal_depth, const uint32_t* history_instance, const float* motion,
+                          int32_t count, const float* history_moments, float* out_rgba, float* out_moments,
+                          uint32_t* out_rgb8, uint32_t out_flags);
+
+typedef struct {
+  int32_t iterations, normal_power;             /* as prt_denoise_params: 1..8, 0..7 */
+  float sigma_color, sigma_depth, sigma_albedo; /* as prt_denoise_params; sigma_color is in standard deviations here */
+  float color_decay;    /* sigma_color is multiplied by this after every iteration; > 0, finite; default 1
+                           (0.5 is prt_denoise's schedule) */
+  float variance_floor; /* > 0, finite; default 1e-6 */
+} prt_denoise_variance_params;
+
+/* host only, no context: iterations 5, normal_power 3, sigma_color 2, sigma_depth 0.1, sigma_albedo 0.25,
+ * color_decay 1, variance_floor 1e-6 */
+int prt_denoise_variance_defaults(prt_denoise_variance_params* out);
+
+/* (ABI 10, additive) prt_denoise with the colour weight scaled by the variance of `moments` (its z; x, y and w are not
+ * read).  Iteration i has step 2^i, I_0 = color, V_0 = moments.z; the taps, their order, the B3 weights, the centre
+ * weight, the normal, depth and albedo weights and the miss pass-through are prt_denoise's.  Per hit pixel p:
+ *   Vp = max(G / g, variance_floor) with G = sum g_q * V_i(q), g = sum g_q over the hits of the 3x3 neighbourhood of
+ *   p inside the image (row-major; g_q = 1/16 corner, 1/8 edge, 1/4 centre)
+ *   wc = 1 / (1 + c2 / (sc_i * sc_i * Vp)), sc_0 = sigma_color, sc_{i+1} = sc_i * color_decay (host, float)
+ *   V_{i+1}(p) = (sum w * w * V_i(q)) / ((sum w) * (sum w)) over the kept taps; a miss keeps its V
+ * out_rgba.w is copied from color_rgba; out_variance (float W*H, may be NULL) receives the last V.  out_rgba may be
+ * color_rgba.  With moments.z == 1 everywhere, variance_floor <= 1, color_decay 0.5 and iterations 1 the colour output
+ * is prt_denoise's bit for bit.  albedo_rgba may be NULL when sigma_albedo == 0.  Host / device pointers,
+ * PRT_OUT_TIMED (ms[1] prep, ms[2 + i] iteration i of prt_denoise_timings), frames in flight and sharded contexts: as
+ * prt_denoise. */
+int prt_denoise_variance(prt_ctx* ctx, const prt_denoise_variance_params* params, int32_t width, int32_t height,
+                         const float* color_rgba, const float* moments, const float* albedo_rgba,
+                         const float* normal_depth, float* out_rgba, float* out_variance, uint32_t* out_rgb8,
+                         uint32_t out_flags);
 
 /* ---- shading-function probe (ABI 10): the device's own BRDF functions (the ones the shading kernels inline) on
  * n host records, for known-answer tests of the BRDF restatement (Core/BRDF.cpp).  Record k: in[24 k ..], out[8 k ..].

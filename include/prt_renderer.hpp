@@ -352,6 +352,7 @@ class Renderer {
     hist_ = out;
     hist_nd_.swap(normal_depth);
     hist_ids_.clear();  // (a following TickTemporalMotion() starts a new history)
+    hist_mom_.clear();  // (and so does a following TickTemporalVariance())
     hist_cam_ = cam;
     history.swap(out);
   }
@@ -377,7 +378,7 @@ class Renderer {
     for (const GameObject& g : scene.gameobjects) xf.insert(xf.end(), g.transform.begin(), g.transform.end());
     screen8.assign(n, 0u);
     const int32_t count = (int32_t)scene.gameobjects.size();
-    if (hist_.empty() || hist_ids_.empty() || hist_xf_.size() != xf.size() || count == 0) {
+    if (hist_.empty() || hist_ids_.empty() || !hist_mom_.empty() || hist_xf_.size() != xf.size() || count == 0) {
       check(prt_reproject_motion(ctx_, &params, width_, height_, &cam, accumulator.data(), normal_depth.data(),
                                  ids.data(), nullptr, nullptr, nullptr, nullptr, nullptr, 0, out.data(),
                                  screen8.data(), 0u));
@@ -392,12 +393,71 @@ class Renderer {
     hist_nd_.swap(normal_depth);
     hist_ids_.swap(ids);
     hist_xf_.swap(xf);
+    hist_mom_.clear();  // (a following TickTemporalVariance() starts a new history)
     hist_cam_ = cam;
     history.swap(out);
   }
-  void ResetTemporal() {  // the next TickTemporal() / TickTemporalMotion() starts a new history
+  static prt_temporal_params TemporalDefaults() {
+    prt_temporal_params p{};
+    check(prt_temporal_defaults(&p));
+    return p;
+  }
+  static prt_denoise_variance_params DenoiseVarianceDefaults() {
+    prt_denoise_variance_params p{};
+    check(prt_denoise_variance_defaults(&p));
+    return p;
+  }
+  // TickTemporalMotion() with the luminance moments carried along (prt_reproject_moments) and the result filtered by
+  // the variance-guided a-trous filter (prt_denoise_variance): filtered gets the filtered float4 image, screen8 its
+  // 0x00RRGGBB pixels, history the unfiltered reprojection output.  The unfiltered output and its moments are the
+  // next call's history (the filtered image is not fed back).  A changed instance count, ResetTemporal() or a
+  // preceding TickTemporal() / TickTemporalMotion() starts a new history.
+  void TickTemporalVariance(std::vector<float>& filtered, std::vector<uint32_t>& screen8, std::vector<float>& history,
+                            const prt_temporal_params& params = TemporalDefaults(),
+                            const prt_denoise_variance_params& filter = DenoiseVarianceDefaults()) {
+    if (isPostProcessed)
+      throw Error(PRT_ERR_INVALID_ARGUMENT,
+                  "temporal reprojection is defined for the plane projection only (isPostProcessed is set)");
+    scene.UploadInstances(ctx_);
+    const prt_camera cam = camera.Plane();
+    check(prt_set_camera(ctx_, &cam));
+    check(prt_reset_accumulation(ctx_, 1));
+    Tick();
+    const size_t n = (size_t)width_ * height_;
+    std::vector<float> albedo(4 * n, 0.0f), normal_depth(4 * n, 0.0f), out(4 * n, 0.0f), mom(4 * n, 0.0f), xf;
+    std::vector<uint32_t> ids(n, 0u);
+    check(prt_render_aov_ids(ctx_, width_, height_, NORMALMAPPED ? PRT_FLAG_NORMALMAP : 0u, albedo.data(),
+                             normal_depth.data(), ids.data(), 0u));
+    for (const GameObject& g : scene.gameobjects) xf.insert(xf.end(), g.transform.begin(), g.transform.end());
+    const int32_t count = (int32_t)scene.gameobjects.size();
+    if (hist_.empty() || hist_ids_.empty() || hist_mom_.empty() || hist_xf_.size() != xf.size() || count == 0) {
+      check(prt_reproject_moments(ctx_, &params, width_, height_, &cam, accumulator.data(), normal_depth.data(),
+                                  ids.data(), nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, out.data(),
+                                  mom.data(), nullptr, 0u));
+    } else {
+      std::vector<float> motion(12 * (size_t)count);
+      check(prt_instance_motion(xf.data(), hist_xf_.data(), count, motion.data()));
+      check(prt_reproject_moments(ctx_, &params, width_, height_, &cam, accumulator.data(), normal_depth.data(),
+                                  ids.data(), &hist_cam_, hist_.data(), hist_nd_.data(), hist_ids_.data(),
+                                  motion.data(), count, hist_mom_.data(), out.data(), mom.data(), nullptr, 0u));
+    }
+    filtered.assign(4 * n, 0.0f);
+    screen8.assign(n, 0u);
+    check(prt_denoise_variance(ctx_, &filter, width_, height_, out.data(), mom.data(), albedo.data(),
+                               normal_depth.data(), filtered.data(), nullptr, screen8.data(), 0u));
+    hist_ = out;
+    hist_nd_.swap(normal_depth);
+    hist_ids_.swap(ids);
+    hist_xf_.swap(xf);
+    hist_mom_.swap(mom);
+    hist_cam_ = cam;
+    history.swap(out);
+  }
+  // the next TickTemporal() / TickTemporalMotion() / TickTemporalVariance() starts a new history
+  void ResetTemporal() {
     hist_.clear();
     hist_ids_.clear();
+    hist_mom_.clear();
   }
 
   uint32_t Flags() const {
@@ -419,6 +479,7 @@ class Renderer {
   prt_camera hist_cam_{};              // ... and the camera they were made with
   std::vector<uint32_t> hist_ids_;     // TickTemporalMotion's: the previous instance ids (empty: no such history)
   std::vector<float> hist_xf_;         // ... and the previous instance transforms (16 floats each)
+  std::vector<float> hist_mom_;        // TickTemporalVariance's: the previous moments (empty: no such history)
 };
 
 }  // namespace prt

@@ -26,6 +26,7 @@
 #include "prt_rccl.h"
 #include "prt_refit.h"
 #include "prt_temporal.h"
+#include "prt_variance.h"
 
 using namespace prt;
 
@@ -364,6 +365,9 @@ struct prt_ctx {
   // instance ids and motion (prt_render_aov_ids / prt_reproject_motion): the id output's staging, the staging of host
   // id images (this view's, the previous view's) and the motion matrices on the device
   DevBuf aov_ids, rp_ids[2], rp_motion;
+  // moments and variance (prt_reproject_moments / prt_denoise_variance): the staging of host moments images (the
+  // previous one, the output; the filter's input) and of the filter's variance output
+  DevBuf rp_mom[2], dn_mom, dn_var;
 };
 
 namespace {
@@ -2681,6 +2685,211 @@ int prt_reproject_motion(prt_ctx* c, const prt_reproject_params* p, int32_t W, i
   HIP_TRY(launch_reproject_motion(c->stream, P));
   if (!dev) {
     if (out_rgba) HIP_TRY(hipMemcpyAsync(out_rgba, dst, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (out_rgb8) HIP_TRY(hipMemcpyAsync(out_rgb8, dst8, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  return PRT_OK;
+}
+
+// ---- luminance moments and the variance-guided filter (prt_variance.hip)
+int prt_temporal_defaults(prt_temporal_params* out) {
+  if (!out) return fail(PRT_ERR_INVALID_ARGUMENT, "out is NULL");
+  out->depth_tol = 0.05f;
+  out->normal_min = 0.9f;
+  out->max_history = 16.0f;
+  out->clamp_k = 0.0f;
+  out->min_temporal = 4.0f;
+  return PRT_OK;
+}
+
+int prt_reproject_moments(prt_ctx* c, const prt_temporal_params* p, int32_t W, int32_t H, const prt_camera* cam,
+                          const float* color, const float* normal_depth, const uint32_t* instance,
+                          const prt_camera* prev_cam, const float* history, const float* history_nd,
+                          const uint32_t* history_inst, const float* motion, int32_t count, const float* history_mom,
+                          float* out_rgba, float* out_mom, uint32_t* out_rgb8, uint32_t out_flags) {
+  if (!c || !p || !cam || !color || !normal_depth || !instance || !out_mom || (!out_rgba && !out_rgb8) || W <= 0 ||
+      H <= 0 || W > 16384 || H > 16384)
+    return fail(PRT_ERR_INVALID_ARGUMENT, "bad reproject arguments");
+  if (!sigma_ok(p->depth_tol, true) || !(p->normal_min >= -1.0f && p->normal_min <= 1.0f) ||
+      !std::isfinite(p->max_history) || p->max_history < 1.0f || !sigma_ok(p->clamp_k, true) ||
+      !std::isfinite(p->min_temporal) || p->min_temporal < 1.0f)
+    return fail(PRT_ERR_INVALID_ARGUMENT, "temporal parameters out of range");
+  const int given = (prev_cam ? 1 : 0) + (history ? 1 : 0) + (history_nd ? 1 : 0) + (motion ? 1 : 0) +
+                    (count ? 1 : 0) + (history_mom ? 1 : 0);
+  if (count < 0 || (given != 0 && given != 6) || (given == 0 && history_inst))
+    return fail(PRT_ERR_INVALID_ARGUMENT,
+                "prev_camera, history_rgba, history_normal_depth, motion, count > 0 and history_moments go together");
+  if (out_rgba == color)  // the clamp and the spatial estimate read the neighbours of color_rgba
+    return fail(PRT_ERR_INVALID_ARGUMENT, "out_rgba must not be color_rgba");
+  if (out_rgba && (out_rgba == normal_depth || out_rgba == out_mom ||
+                   (given && (out_rgba == history || out_rgba == history_nd || out_rgba == history_mom))))
+    return fail(PRT_ERR_INVALID_ARGUMENT, "out_rgba must not be an input or out_moments");
+  if (out_mom == color || out_mom == normal_depth ||
+      (given && (out_mom == history_mom || out_mom == history || out_mom == history_nd)))
+    return fail(PRT_ERR_INVALID_ARGUMENT, "out_moments must not be an input");
+  if (out_rgb8 && (out_rgb8 == instance || (history_inst && out_rgb8 == history_inst)))
+    return fail(PRT_ERR_INVALID_ARGUMENT, "out_rgb8 must not be an instance buffer");
+  PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t n = (size_t)W * H, bytes = n * sizeof(float4);
+  const bool dev = (out_flags & PRT_OUT_DEVICE) != 0;
+  const float4* src[4] = {reinterpret_cast<const float4*>(color), reinterpret_cast<const float4*>(normal_depth),
+                          reinterpret_cast<const float4*>(history), reinterpret_cast<const float4*>(history_nd)};
+  const uint32_t* ids[2] = {instance, history_inst};
+  const float4* hmom = reinterpret_cast<const float4*>(history_mom);
+  float4* dst = reinterpret_cast<float4*>(out_rgba);
+  float4* dstm = reinterpret_cast<float4*>(out_mom);
+  uint32_t* dst8 = out_rgb8;
+  if (!dev) {  // host images: staged in context buffers
+    for (int k = 0; k < 4; k++) {
+      if (!src[k]) continue;
+      HIP_TRY(c->rp_in[k].ensure(bytes));
+      HIP_TRY(hipMemcpyAsync(c->rp_in[k].p, src[k], bytes, hipMemcpyHostToDevice, c->stream));
+      src[k] = c->rp_in[k].as<float4>();
+    }
+    for (int k = 0; k < 2; k++) {
+      if (!ids[k]) continue;
+      HIP_TRY(c->rp_ids[k].ensure(n * 4));
+      HIP_TRY(hipMemcpyAsync(c->rp_ids[k].p, ids[k], n * 4, hipMemcpyHostToDevice, c->stream));
+      ids[k] = c->rp_ids[k].as<uint32_t>();
+    }
+    if (hmom) {
+      HIP_TRY(c->rp_mom[0].ensure(bytes));
+      HIP_TRY(hipMemcpyAsync(c->rp_mom[0].p, hmom, bytes, hipMemcpyHostToDevice, c->stream));
+      hmom = c->rp_mom[0].as<float4>();
+    }
+    HIP_TRY(c->rp_mom[1].ensure(bytes));
+    dstm = c->rp_mom[1].as<float4>();
+    if (out_rgba) { HIP_TRY(c->rp_out.ensure(bytes)); dst = c->rp_out.as<float4>(); }
+    if (out_rgb8) { HIP_TRY(c->rp_rgb8.ensure(n * 4)); dst8 = c->rp_rgb8.as<uint32_t>(); }
+  }
+  if (given) {  // the matrices: copied into a pinned staging buffer now, uploaded in stream order (no host wait)
+    const size_t mb = 12 * sizeof(float) * (size_t)count;
+    HIP_TRY(c->rp_motion.ensure(mb));
+    StageSlot* st = nullptr;
+    const int rc = stage_acquire(c, mb, st);
+    if (rc) return rc;
+    std::memcpy(st->p, motion, mb);
+    HIP_TRY(hipMemcpyAsync(c->rp_motion.p, st->p, mb, hipMemcpyHostToDevice, c->stream));
+    const int rr = stage_release(c, *st, c->stream);
+    if (rr) return rr;
+  }
+  MomentsPass Q{};
+  ReprojectPass& R = Q.M.R;
+  R.W = W;
+  R.H = H;
+  R.depth_tol = p->depth_tol;
+  R.normal_min = p->normal_min;
+  R.max_history = p->max_history;
+  make_reproject_pass(R, *cam, prev_cam);
+  R.color = src[0];
+  R.nd = src[1];
+  R.hist = src[2];
+  R.hist_nd = src[3];
+  R.out = dst;
+  R.rgb8 = dst8;
+  Q.M.inst = ids[0];
+  Q.M.hist_inst = ids[1];
+  Q.M.motion = given ? c->rp_motion.as<float4>() : nullptr;
+  Q.M.count = count;
+  Q.hist_mom = hmom;
+  Q.mom = dstm;
+  Q.clamp_k = p->clamp_k;
+  Q.min_temporal = p->min_temporal;
+  HIP_TRY(launch_reproject_moments(c->stream, Q));
+  if (!dev) {
+    if (out_rgba) HIP_TRY(hipMemcpyAsync(out_rgba, dst, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out_mom, dstm, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (out_rgb8) HIP_TRY(hipMemcpyAsync(out_rgb8, dst8, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  return PRT_OK;
+}
+
+int prt_denoise_variance_defaults(prt_denoise_variance_params* out) {
+  if (!out) return fail(PRT_ERR_INVALID_ARGUMENT, "out is NULL");
+  out->iterations = 5;
+  out->normal_power = 3;
+  out->sigma_color = 2.0f;
+  out->sigma_depth = 0.1f;
+  out->sigma_albedo = 0.25f;
+  out->color_decay = 1.0f;
+  out->variance_floor = 1e-6f;
+  return PRT_OK;
+}
+
+int prt_denoise_variance(prt_ctx* c, const prt_denoise_variance_params* p, int32_t W, int32_t H, const float* color,
+                         const float* moments, const float* albedo, const float* normal_depth, float* out_rgba,
+                         float* out_variance, uint32_t* out_rgb8, uint32_t out_flags) {
+  if (!c || !p || !color || !moments || !normal_depth || (!out_rgba && !out_rgb8) || W <= 0 || H <= 0 || W > 16384 ||
+      H > 16384)
+    return fail(PRT_ERR_INVALID_ARGUMENT, "bad denoise arguments");
+  if (p->iterations < 1 || p->iterations > 8 || p->normal_power < 0 || p->normal_power > 7 ||
+      !sigma_ok(p->sigma_color, false) || !sigma_ok(p->sigma_depth, false) || !sigma_ok(p->sigma_albedo, true) ||
+      !sigma_ok(p->color_decay, false) || !sigma_ok(p->variance_floor, false))
+    return fail(PRT_ERR_INVALID_ARGUMENT, "denoise parameters out of range");
+  const bool use_albedo = p->sigma_albedo > 0.0f;
+  if (use_albedo && !albedo) return fail(PRT_ERR_INVALID_ARGUMENT, "albedo is NULL with sigma_albedo > 0");
+  PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t n = (size_t)W * H, bytes = n * sizeof(float4);
+  const bool dev = (out_flags & PRT_OUT_DEVICE) != 0, timed = (out_flags & PRT_OUT_TIMED) != 0;
+  const float4* src[3] = {reinterpret_cast<const float4*>(color), reinterpret_cast<const float4*>(normal_depth),
+                          use_albedo ? reinterpret_cast<const float4*>(albedo) : nullptr};
+  const float4* mom = reinterpret_cast<const float4*>(moments);
+  float4* dst = reinterpret_cast<float4*>(out_rgba);
+  float* dstv = out_variance;
+  uint32_t* dst8 = out_rgb8;
+  if (!dev) {  // host images: staged in context buffers
+    for (int k = 0; k < 3; k++) {
+      if (!src[k]) continue;
+      HIP_TRY(c->dn_in[k].ensure(bytes));
+      HIP_TRY(hipMemcpyAsync(c->dn_in[k].p, src[k], bytes, hipMemcpyHostToDevice, c->stream));
+      src[k] = c->dn_in[k].as<float4>();
+    }
+    HIP_TRY(c->dn_mom.ensure(bytes));
+    HIP_TRY(hipMemcpyAsync(c->dn_mom.p, mom, bytes, hipMemcpyHostToDevice, c->stream));
+    mom = c->dn_mom.as<float4>();
+    if (out_rgba) { HIP_TRY(c->dn_out.ensure(bytes)); dst = c->dn_out.as<float4>(); }
+    if (out_variance) { HIP_TRY(c->dn_var.ensure(n * 4)); dstv = c->dn_var.as<float>(); }
+    if (out_rgb8) { HIP_TRY(c->dn_rgb8.ensure(n * 4)); dst8 = c->dn_rgb8.as<uint32_t>(); }
+  }
+  HIP_TRY(c->dn_geo.ensure(bytes));
+  HIP_TRY(c->dn_pp[0].ensure(bytes));  // (rgb, V): iteration i reads dn_pp[i & 1]
+  if (p->iterations > 1) HIP_TRY(c->dn_pp[1].ensure(bytes));
+  int rc = PRT_OK;
+  if (timed && (rc = dn_event(c, 2))) return rc;
+  HIP_TRY(launch_denoise_var_prep(c->stream, W, H, src[1], src[0], mom, c->dn_geo.as<float4>(),
+                                  c->dn_pp[0].as<float4>()));
+  if (timed && (rc = dn_event(c, 3))) return rc;
+  float sc = p->sigma_color;
+  for (int32_t i = 0; i < p->iterations; i++) {
+    const bool last = i == p->iterations - 1;
+    VarDenoisePass Q{};
+    DenoisePass& P = Q.D;
+    P.W = W;
+    P.H = H;
+    P.step = 1 << i;
+    P.normal_power = p->normal_power;
+    P.sc2 = sc * sc;
+    P.sigma_depth = p->sigma_depth;
+    P.sa2 = p->sigma_albedo * p->sigma_albedo;
+    P.color = c->dn_pp[i & 1].as<float4>();
+    P.geo = c->dn_geo.as<float4>();
+    P.albedo = src[2];
+    P.out = last ? dst : c->dn_pp[(i + 1) & 1].as<float4>();
+    P.rgb8 = last ? dst8 : nullptr;
+    Q.variance_floor = p->variance_floor;
+    Q.restore = last ? src[0] : nullptr;
+    Q.variance = last ? dstv : nullptr;
+    HIP_TRY(launch_denoise_var_pass(c->stream, Q));
+    if (timed && (rc = dn_event(c, 4 + i))) return rc;
+    sc = sc * p->color_decay;
+  }
+  if (timed) c->dn_timed_passes = p->iterations;
+  if (!dev) {
+    if (out_rgba) HIP_TRY(hipMemcpyAsync(out_rgba, dst, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (out_variance) HIP_TRY(hipMemcpyAsync(out_variance, dstv, n * 4, hipMemcpyDeviceToHost, c->stream));
     if (out_rgb8) HIP_TRY(hipMemcpyAsync(out_rgb8, dst8, n * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
   }

@@ -34,6 +34,7 @@ EXPORTS = [
     "prt_render_aov", "prt_denoise_defaults", "prt_denoise", "prt_denoise_timings",
     "prt_reproject_defaults", "prt_reproject", "prt_primary_rays", "prt_shadow_reuse",
     "prt_render_aov_ids", "prt_instance_motion", "prt_reproject_motion",
+    "prt_temporal_defaults", "prt_reproject_moments", "prt_denoise_variance_defaults", "prt_denoise_variance",
 ]
 SHARD_ID_BYTES = 128
 SHARD_NONE, SHARD_RCCL, SHARD_GROUP = 0, 1, 2  # prt_shard_info.transport
@@ -109,6 +110,21 @@ class DenoiseParams(C.Structure):
 class ReprojectParams(C.Structure):
     """prt_reproject_params: the relative depth tolerance, the least normal dot and the history cap (>= 1)."""
     _fields_ = [("depth_tol", C.c_float), ("normal_min", C.c_float), ("max_history", C.c_float)]
+
+
+class TemporalParams(C.Structure):
+    """prt_temporal_params: prt_reproject_params, the clamp's width in sigmas (0: none) and the history length from
+    which the moments give the variance (>= 1)."""
+    _fields_ = [("depth_tol", C.c_float), ("normal_min", C.c_float), ("max_history", C.c_float),
+                ("clamp_k", C.c_float), ("min_temporal", C.c_float)]
+
+
+class DenoiseVarianceParams(C.Structure):
+    """prt_denoise_variance_params: prt_denoise_params, the factor sigma_color takes after every iteration and the
+    least variance (> 0)."""
+    _fields_ = [("iterations", C.c_int32), ("normal_power", C.c_int32), ("sigma_color", C.c_float),
+                ("sigma_depth", C.c_float), ("sigma_albedo", C.c_float), ("color_decay", C.c_float),
+                ("variance_floor", C.c_float)]
 
 
 class ShardInfo(C.Structure):
@@ -194,6 +210,12 @@ def load():
         "prt_instance_motion": ([vp, vp, i32, vp], C.c_int),
         "prt_reproject_motion": ([vp, C.POINTER(ReprojectParams), i32, i32, C.POINTER(CameraDesc), vp, vp, vp,
                                   C.POINTER(CameraDesc), vp, vp, vp, vp, i32, vp, vp, u32], C.c_int),
+        "prt_temporal_defaults": ([C.POINTER(TemporalParams)], C.c_int),
+        "prt_reproject_moments": ([vp, C.POINTER(TemporalParams), i32, i32, C.POINTER(CameraDesc), vp, vp, vp,
+                                   C.POINTER(CameraDesc), vp, vp, vp, vp, i32, vp, vp, vp, vp, u32], C.c_int),
+        "prt_denoise_variance_defaults": ([C.POINTER(DenoiseVarianceParams)], C.c_int),
+        "prt_denoise_variance": ([vp, C.POINTER(DenoiseVarianceParams), i32, i32, vp, vp, vp, vp, vp, vp, vp, u32],
+                                 C.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

@@ -105,6 +105,30 @@ def reproject_defaults(**overrides):
     return rp
 
 
+def temporal_defaults(**overrides):
+    """prt_temporal_params at the library's defaults (prt_temporal_defaults); keyword overrides set single fields
+    (depth_tol, normal_min, max_history, clamp_k, min_temporal)."""
+    tp = _lib.TemporalParams()
+    check(_lib.load().prt_temporal_defaults(C.byref(tp)))
+    for k, v in overrides.items():
+        if k not in dict(tp._fields_):
+            raise TypeError(f"prt_temporal_params has no field {k!r}")
+        setattr(tp, k, v)
+    return tp
+
+
+def denoise_variance_defaults(**overrides):
+    """prt_denoise_variance_params at the library's defaults (prt_denoise_variance_defaults); keyword overrides set
+    single fields (iterations, normal_power, sigma_color, sigma_depth, sigma_albedo, color_decay, variance_floor)."""
+    dp = _lib.DenoiseVarianceParams()
+    check(_lib.load().prt_denoise_variance_defaults(C.byref(dp)))
+    for k, v in overrides.items():
+        if k not in dict(dp._fields_):
+            raise TypeError(f"prt_denoise_variance_params has no field {k!r}")
+        setattr(dp, k, v)
+    return dp
+
+
 def _camera_desc(cam):
     """A Camera or a _lib.CameraDesc -> a copy of the prt_camera struct (the caller may go on moving its camera)."""
     cd = _lib.CameraDesc()
@@ -499,6 +523,60 @@ class Context:
                                           pj, pm, count, po, p8, _lib.OUT_DEVICE if device_out else 0))
         return out, rgb8
 
+    # -- luminance moments and the variance-guided filter (include/prt.h prt_reproject_moments / prt_denoise_variance)
+    def reproject_moments(self, color, normal_depth, instance, camera, history=None, history_normal_depth=None,
+                          prev_camera=None, history_instance=None, motion=None, history_moments=None, *, width,
+                          height, params=None, device_out=False, out=None, moments=None, rgb8=None):
+        """reproject_motion() that carries the luminance moments with the history: `history_moments` is the previous
+        call's moments output and belongs to the all-or-nothing history group; `instance` is always required; `out`
+        must not be `color`.  Returns (out[n,4], moments[n,4], rgb8[n]); moments is (m1, m2, variance, 0)."""
+        tp = params if params is not None else temporal_defaults()
+        n = width * height
+        cam = _camera_desc(camera)
+        prev = C.byref(_camera_desc(prev_camera)) if prev_camera is not None else None
+        mo = _f32(motion).reshape(-1, 12) if motion is not None else None
+        pm, count = (mo.ctypes.data, len(mo)) if mo is not None else (None, 0)
+        if not device_out:
+            imgs = [_f32(a).reshape(n, 4) if a is not None else None
+                    for a in (color, normal_depth, history, history_normal_depth, history_moments)]
+            ids = [np.ascontiguousarray(a, np.uint32).reshape(n) if a is not None else None
+                   for a in (instance, history_instance)]
+            out = np.zeros((n, 4), F32)
+            moments = np.zeros((n, 4), F32)
+            rgb8 = np.zeros(n, np.uint32)
+            pc, pn, ph, pg, pq, pi, pj = (a.ctypes.data if a is not None else None for a in imgs + ids)
+            po, pmo, p8 = out.ctypes.data, moments.ctypes.data, rgb8.ctypes.data
+        else:
+            pc, pn, ph, pg, pq, pi, pj, po, pmo, p8 = (color, normal_depth, history, history_normal_depth,
+                                                       history_moments, instance, history_instance, out, moments,
+                                                       rgb8)
+        check(self.L.prt_reproject_moments(self.h, C.byref(tp), width, height, C.byref(cam), pc, pn, pi, prev, ph, pg,
+                                           pj, pm, count, pq, po, pmo, p8, _lib.OUT_DEVICE if device_out else 0))
+        return out, moments, rgb8
+
+    def denoise_variance(self, color, moments, albedo, normal_depth, width, height, params=None, device_out=False,
+                         out=None, variance=None, rgb8=None, timed=False, want_variance=True):
+        """denoise() whose colour weight is scaled by the variance in `moments` (reproject_moments()' output); returns
+        (out[n,4], variance[n] or None, rgb8[n]).  device_out: every image is a raw device pointer, out / variance /
+        rgb8 are where the results go (out or rgb8 and variance may be None; out may be the same pointer as color)."""
+        dp = params if params is not None else denoise_variance_defaults()
+        n = width * height
+        of = (_lib.OUT_DEVICE if device_out else 0) | (_lib.OUT_TIMED if timed else 0)
+        if not device_out:
+            color, moments = _f32(color).reshape(n, 4), _f32(moments).reshape(n, 4)
+            normal_depth = _f32(normal_depth).reshape(n, 4)
+            albedo = _f32(albedo).reshape(n, 4) if albedo is not None else None
+            out = np.zeros((n, 4), F32)
+            variance = np.zeros(n, F32) if want_variance else None
+            rgb8 = np.zeros(n, np.uint32)
+            args = (color.ctypes.data, moments.ctypes.data, albedo.ctypes.data if albedo is not None else None,
+                    normal_depth.ctypes.data, out.ctypes.data, variance.ctypes.data if want_variance else None,
+                    rgb8.ctypes.data)
+        else:
+            args = (color, moments, albedo, normal_depth, out, variance, rgb8)
+        check(self.L.prt_denoise_variance(self.h, C.byref(dp), width, height, *args, of))
+        return out, variance, rgb8
+
     def intersect(self, O, D, tmax=None):
         O, D = _f32(O), _f32(D)
         n = O.shape[0]
@@ -579,7 +657,8 @@ class Renderer:
         self.screen = np.zeros(width * height, np.uint32)
         self.average = np.zeros((width * height, 4), F32)
         self.last_stats = None
-        self._temporal = None  # TickTemporal's history: (width, height, out, normal_depth, camera[, ids, transforms])
+        # TickTemporal's history: (width, height, out, normal_depth, camera[, ids, transforms[, moments]])
+        self._temporal = None
         self.Init()
 
     def Init(self):
@@ -663,8 +742,39 @@ class Renderer:
         self._temporal = (W, H, out, nd, cam, ids, xf)
         return out, rgb8
 
+    def TickTemporalVariance(self, params=None, filter_params=None):
+        """TickTemporal(motion=True) with the luminance moments carried along (reproject_moments, `params`:
+        temporal_defaults()) and the result filtered by denoise_variance (`filter_params`:
+        denoise_variance_defaults()).  Returns (filtered, screen, history): the filtered float4 image, its 0x00RRGGBB
+        pixels and the unfiltered reprojection output.  The unfiltered output and its moments are the next call's
+        history (the filtered image is not fed back).  A changed image size or instance count, ResetTemporal() or a
+        preceding TickTemporal() starts a new history."""
+        if self.isPostProcessed:
+            raise ValueError(PANINI_REPROJECT)
+        W, H = self.width, self.height
+        self.ctx.set_instances(self.scene.blases)
+        self.ctx.set_camera(self.camera)
+        self.ctx.reset_accumulation(full=True)
+        self.Tick()
+        alb, nd, ids = self.ctx.render_aov_ids(W, H, _lib.FLAG_NORMALMAP if self.NORMALMAPPED else 0)
+        cam = _camera_desc(self.camera)
+        xf = _f32(np.stack([T for _, T in self.scene.blases])).reshape(-1, 16).copy()
+        t = self._temporal
+        if t is not None and (t[:2] != (W, H) or len(t) != 8 or len(t[6]) != len(xf)):
+            t = None
+        if t is None:
+            out, mom, _ = self.ctx.reproject_moments(self.average, nd, ids, cam, width=W, height=H, params=params)
+        else:
+            hist, hist_nd, prev, hist_ids, prev_xf, hist_mom = t[2:]
+            out, mom, _ = self.ctx.reproject_moments(self.average, nd, ids, cam, hist, hist_nd, prev, hist_ids,
+                                                     instance_motion(xf, prev_xf), hist_mom, width=W, height=H,
+                                                     params=params)
+        self._temporal = (W, H, out, nd, cam, ids, xf, mom)
+        filtered, _, rgb8 = self.ctx.denoise_variance(out, mom, alb, nd, W, H, filter_params, want_variance=False)
+        return filtered, rgb8, out
+
     def ResetTemporal(self):
-        """The next TickTemporal() starts a new history."""
+        """The next TickTemporal() / TickTemporalVariance() starts a new history."""
         self._temporal = None
 
     def Capture(self, path):
