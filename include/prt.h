@@ -258,6 +258,17 @@ int prt_primary_rays(prt_ctx* ctx, uint64_t* traced, uint64_t* reused, int32_t r
  * summed over its members); reset != 0 zeroes it after reading.  A skipped shadow ray is still a shadow ray of its
  * path: prt_ray_totals and prt_stats count it. */
 int prt_shadow_reuse(prt_ctx* ctx, uint64_t* reused, int32_t reset);
+/* Dead shadow-ray counter (additive within ABI 10).  A next-event shadow ray is dead when the factor its visibility
+ * answer is multiplied by is exactly zero: PRT_FLAG_LIGHTED is off, or every channel of its unoccluded contribution
+ * compares equal to zero (the light is behind the shading normal, the hit point is outside the spot's cone, the
+ * light is black).  Renders count such rays of the point, directional and spot lights instead of tracing them
+ * (bit-identical images; PRT_DEAD_SHADOW=0 in the environment traces them all; the debug render modes cast no
+ * shadow rays, and an area light's own ray is traced as ever).  Rays under the light-visibility record
+ * (prt_shadow_reuse) are asked, learned and counted there as before.  dead: the shadow rays skipped this way so
+ * far, counted on the device; waits like prt_shadow_reuse (a local group: summed over its members); reset != 0
+ * zeroes it after reading.  A dead shadow ray is still a shadow ray of its path: prt_ray_totals and prt_stats count
+ * it. */
+int prt_shadow_dead(prt_ctx* ctx, uint64_t* dead, int32_t reset);
 
 /* ---- checkpoint / resume of the progressive accumulation (the reference keeps it in memory only) ----
  * The accumulation state Renderer holds between Ticks (Core/Renderer.h:61-63: accumulator, samplesPerPixel,

@@ -291,6 +291,12 @@ class Renderer {
     check(prt_shadow_reuse(ctx_, &reused, reset ? 1 : 0));
     return reused;
   }
+  // shadow rays counted instead of traced because their contribution is zero so far (prt_shadow_dead; waits)
+  uint64_t ShadowDead(bool reset = false) const {
+    uint64_t dead = 0;
+    check(prt_shadow_dead(ctx_, &dead, reset ? 1 : 0));
+    return dead;
+  }
 
   // First-hit feature buffers of the scene and camera at pixel centres (prt_render_aov): albedo = base colour
   // (w = 1; miss 0), normal_depth = the shading normal as Trace uses it with the hit distance in w (miss

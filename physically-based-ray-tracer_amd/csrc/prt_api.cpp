@@ -945,6 +945,13 @@ bool shadow_reuse_on() {
   const char* e = std::getenv("PRT_SHADOW_REUSE");
   return !(e && std::atoi(e) == 0);
 }
+// Dead shadow rays (prt_wave2.hip nee_live) are counted instead of traced by every shading kernel of render mode 0,
+// outside the rays the light-visibility record answers for; PRT_DEAD_SHADOW=0 traces them all (A/B runs, tests).
+// Read per call
+bool dead_shadow_on() {
+  const char* e = std::getenv("PRT_DEAD_SHADOW");
+  return !(e && std::atoi(e) == 0);
+}
 // the key of the primary hits a call with scene S and tile map M would trace
 PrimKey prim_key(const prt_ctx* c, const SceneDev& S, const TileMap& M) {
   PrimKey k;
@@ -1107,6 +1114,7 @@ int enqueue_render_body(prt_ctx* c, const prt_render_params* p, const TileMap& M
     ws0.wb.pmode = kPrimTrace;
     ws0.wb.lvis = nullptr;
     ws0.wb.lslot = iters + 1;
+    ws0.wb.dead = dead_shadow_on() ? 1u : 0u;
     if (R.preuse && nb > 0) {
       const PrimKey key = prim_key(c, S, M);
       const uint64_t px = tile_image_pixels(M);  // the tile map's entries that have a pixel (and a ray)
@@ -2109,6 +2117,26 @@ int prt_shadow_reuse(prt_ctx* c, uint64_t* reused, int32_t reset) {
   }
   HIP_TRY(hipSetDevice(c->device));
   *reused = n;
+  return PRT_OK;
+}
+
+int prt_shadow_dead(prt_ctx* c, uint64_t* dead, int32_t reset) {
+  if (!c || !dead) return fail(PRT_ERR_INVALID_ARGUMENT, "bad dead shadow ray counter arguments");
+  PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
+  std::vector<prt_ctx*> all{c};
+  all.insert(all.end(), c->members.begin(), c->members.end());
+  uint64_t n = 0;
+  for (prt_ctx* m : all) {  // the device's count (prt_wave2.hip dead_total), 16 bytes behind the ray totals
+    HIP_TRY(hipSetDevice(m->device));
+    unsigned long long h = 0;
+    void* dev = reinterpret_cast<unsigned long long*>(ray_totals_dev(m) + 1) + 1;
+    HIP_TRY(hipMemcpyAsync(&h, dev, sizeof(h), hipMemcpyDeviceToHost, m->stream));
+    if (reset) HIP_TRY(hipMemsetAsync(dev, 0, sizeof(h), m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    n += h;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  *dead = n;
   return PRT_OK;
 }
 

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
+
 #include "prt_kernels.h"
 #include "prt_post.h"
 #include "prt_traverse8.h"
@@ -77,8 +79,13 @@ struct WaveBufs {
   // 1 occluded, 2 unoccluded).  Null unless the pass runs with kPrimReuse and the record belongs to phit and to
   // the lights' positions (prt_api.cpp); one copy per wavefront state
   uint2* lvis;
-  uint32_t lslot;          // the iteration whose shadow counter counts the rays answered from lvis (iters + 1)
+  uint32_t lslot;          // the iteration whose shadow counter counts the shadow rays not queued (iters + 1): those
+                           // answered from lvis and the dead ones
+  uint32_t dead;           // skip dead shadow rays (prt_wave2.hip; PRT_DEAD_SHADOW=0 clears it).  In the struct's
+                           // tail padding: the kernel arguments behind a WaveBufs stay where they were
 };
+static_assert(sizeof(WaveBufs) % 8 == 0 && offsetof(WaveBufs, dead) + 4 == sizeof(WaveBufs),
+              "dead fills WaveBufs' tail padding");
 enum : int32_t { kPrimTrace = 0, kPrimDense = 1, kPrimReuse = 2 };
 constexpr uint32_t kParts = 8;  // XCD parts of a traversal launch's live range, one fetch counter each (prt_queue.h)
 constexpr int kMaxIters = 128;  // wavefront iterations per call: bounces <= 64 (AA) / 6 with dielectrics (AA)

@@ -143,6 +143,22 @@ __device__ __forceinline__ V3 nee_contrib(const SceneDev& S, int kind, int k, fl
   return v3(S.dcol[0], S.dcol[1], S.dcol[2]) * nk.x;
 }
 
+// The live shadow rays of an item (bit k = ray k of its light class).  Ray k is dead when PRT_FLAG_LIGHTED is off
+// or every channel of nee_contrib(S, kind, k, nk) compares equal to zero (the cosine clamped to 0, a hit point
+// outside the spot's cone, an underflow, a black light): nee_resolve then adds colour x 0, or nothing, to a sum
+// that starts at +0 and is never -0, so the ray's answer cannot change a bit of the result.  A NaN compares unequal
+// and stays live.
+__device__ __forceinline__ uint32_t nee_live(const SceneDev& S, uint32_t fl, int kind, float4 nk) {
+  if (!(fl & kLighted)) return 0u;
+  const auto nz = [](V3 c) { return !(c.x == 0.0f && c.y == 0.0f && c.z == 0.0f); };
+  if (kind != 0) return nz(nee_contrib(S, kind, 0, nk)) ? 1u : 0u;
+  uint32_t live = 0;
+#pragma unroll
+  for (int k = 0; k < 4; k++)
+    if (nz(nee_contrib(S, 0, k, nk))) live |= 1u << k;
+  return live;
+}
+
 // result after NEE: emissive + throughput(=1) * (BRDF * contribution), the reference's float order.
 // vis bit i = shadow ray i unoccluded.
 __device__ __forceinline__ V3 nee_resolve(const SceneDev& S, int kind, uint32_t vis, V3 e, V3 brdf, float4 nk,

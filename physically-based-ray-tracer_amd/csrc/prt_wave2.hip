@@ -66,6 +66,19 @@
 // store the same bytes in one launch, always with the same values (the pattern of vis8).  Each wavefront state owns
 // its record; the host clears it (hipMemsetAsync on the state's stream, before k_wave_init) when a dense pass has
 // rewritten phit since it was learned or the light positions differ (prt_api.cpp enqueue_render_body).
+//
+// Dead shadow rays (every shading form but the two under the record above; B.dead, PRT_DEAD_SHADOW=0 clears it).  A
+// light-class shadow ray is dead when its visibility answer is multiplied by exactly zero: PRT_FLAG_LIGHTED is off,
+// or every channel of nee_contrib compares equal to zero (prt_path.h nee_live: the cosine clamped to 0, a hit outside
+// the spot's cone, a black light).  The reference traces such rays; their answer cannot change a bit of the result.
+// The shading runs its NEE block first and appends the block's shadow-ray slots behind it: only the live rays are
+// queued, in compact slots, their entries rebuilt from the item's light class and its live mask (queue_live); the
+// dead ones are counted into the shadow counter of iteration iters + 1 (B.lslot, as the rays the record answers) and
+// into the context's running total (prt_shadow_dead), and their visibility bytes keep the "occluded" 0 the shading
+// stores, so the resolve kernels and k_trace2 are what they were.  An item with no live ray stores no hp.  Nothing is
+// kept between calls: deadness depends on the spot direction, the colours and the flags, which do not invalidate
+// the record, and so the rays under the record (iteration 0 of a kPrimReuse pass) are asked, learned and counted as
+// before.  The area light's ray (EXT) is queued as ever.
 #include <cstdio>
 
 #include "prt_launch.h"
@@ -395,6 +408,19 @@ __device__ __forceinline__ void lvis_learn(const WaveBufs& B, uint32_t item, uin
 __device__ __forceinline__ unsigned long long* lvis_total(const SceneDev& S) {
   return reinterpret_cast<unsigned long long*>(S.diag + 8);
 }
+// ... and of the dead shadow rays that were counted instead of queued (prt_shadow_dead): the 8 bytes behind that
+__device__ __forceinline__ unsigned long long* dead_total(const SceneDev& S) {
+  return reinterpret_cast<unsigned long long*>(S.diag + 10);
+}
+// the light-class shadow-queue entries of an item, rebuilt from its light class and its live mask (nee_live) in
+// compact slots from s0 on: ray k of kind 0 goes to point light k, the other kinds have ray 0 alone; vi = the index
+// of the item's visibility word
+__device__ __forceinline__ void queue_live(uint32_t* shq, uint32_t s0, int kind, uint32_t live, uint32_t vi) {
+  const uint32_t l0 = kind == 0 ? 0u : (kind == 2 ? kLightSpot : kLightDir);
+#pragma unroll
+  for (uint32_t k = 0; k < 4; k++)
+    if (live & (1u << k)) shq[s0 + (uint32_t)__popc(live & ((1u << k) - 1u))] = ((l0 + k) << 29) | (4u * vi + k);
+}
 
 // ---- shading of P(iter): NEE set-up -> S(iter), BRDF sample or path-2 start -> P(iter + 1)
 // k_shade2's parameter list as the kernarg segment holds it (explicit arguments in order, each at its natural
@@ -407,8 +433,8 @@ struct Shade2Args {
   uint32_t iter;
 };
 typedef const __attribute__((address_space(4))) Shade2Args* Shade2ArgsPtr;
-// EXT (area light, dielectrics): held to 3 waves/SIMD (167 VGPRs, no spills; unbounded it takes 175 and runs 2
-// waves: C5 frame 135.7 -> 132.4 ms).  The plain form runs 4 waves at its natural 119 VGPRs (forcing 5 spilled
+// EXT (area light, dielectrics): held to 3 waves/SIMD (168 VGPRs, no spills; unbounded it took 175 and ran 2
+// waves: C5 frame 135.7 -> 132.4 ms).  The plain form runs 4 waves at its natural 125 VGPRs (forcing 5 spilled
 // and was 2 % slower).
 // I0 (plain form): iteration 0 of a pass with pmode kPrimReuse and a light-visibility record (B.lvis), an
 // instantiation of its own so that the shading of every other launch carries nothing for it
@@ -486,10 +512,11 @@ __global__ void __launch_bounds__(kBlock, EXT ? 3 : (I0 ? 4 : 1)) k_shade2(Scene
     }
     prefetch(c + gridDim.x);
     // the block's shadow-ray slots, one atomic (I0: of the rays whose answer is not known yet; the known ones are
-    // counted, not queued)
-    const uint32_t s0 = I0 ? block_append_skip(shcnt, (uint32_t)__popc(ask), qcounter(B.ctr, B.lslot, 1, sub),
-                                               lvis_total(S), nr - (uint32_t)__popc(ask), sm)
-                           : block_append(shcnt, nr, sm);
+    // counted, not queued).  Every other form appends behind the NEE block, once it knows which rays are live
+    uint32_t s0 = 0, live = 0;  // (!I0) live: the item's light-class shadow rays to queue, bit k = ray k
+    if constexpr (I0)
+      s0 = block_append_skip(shcnt, (uint32_t)__popc(ask), qcounter(B.ctr, B.lslot, 1, sub), lvis_total(S),
+                             nr - (uint32_t)__popc(ask), sm);
     const uint32_t depth = info & 0xFFu, path = (info >> 8) & 1u;
     uint32_t status = kStMiss, emissive = 0;
     bool next = false;
@@ -501,18 +528,18 @@ __global__ void __launch_bounds__(kBlock, EXT ? 3 : (I0 ? 4 : 1)) k_shade2(Scene
       const V3 I = v3(o.x, o.y, o.z) + hh.x * D;                                             // tiny_bvh.h:586
       const V3 V = -D;
       const HitAttr ha = hit_attributes(Sc, hit_inst(Sc, pk), hit_prim(Sc, pk), hh.y, hh.z, (fl & kNormalMap) != 0);
-      // a shadow ray is queued as (light, visibility index) with the item's hit point I stored once: the traversal
-      // kernel rebuilds it (shadow_of)
-      Bc.hp[item] = make_float4(I.x, I.y, I.z, 0.0f);
       float4 nk;
       const V3 brdf = nee_lights(Sc, fl, kind, I, V, ha.N, ha.m, seed, nk, [&](int k, uint32_t light) {
         if constexpr (I0) {  // compact slots: the asked rays below k come first
           if (ask & (1u << (8 * k)))
             shq[s0 + (uint32_t)__popc(ask & ((1u << (8 * k)) - 1u))] = (light << 29) | (4u * item + (uint32_t)k);
-        } else {
-          shq[s0 + k] = (light << 29) | (4u * item + (uint32_t)k);
         }
       });
+      // dead rays (!I0): counted, not queued; their visibility bytes keep the "occluded" 0 stored below
+      if constexpr (!I0) live = Bc.dead ? nee_live(Sc, fl, kind, nk) : (1u << nr) - 1u;
+      // a shadow ray is queued as (light, visibility index) with the item's hit point I stored once: the traversal
+      // kernel rebuilds it (shadow_of, the only reader: an item that queues no light-class ray needs none)
+      if (I0 || live) Bc.hp[item] = make_float4(I.x, I.y, I.z, 0.0f);
       const V3 e = v3(0.0f, 0.0f, 0.0f) + v3(1.0f, 1.0f, 1.0f) * ha.m.emis;                // :196
       if (e.x != 0.0f || e.y != 0.0f || e.z != 0.0f) {  // otherwise e is +0 and the resolve rebuilds it
         Bc.ne[item] = make_float4(e.x, e.y, e.z, 0.0f);
@@ -570,6 +597,11 @@ __global__ void __launch_bounds__(kBlock, EXT ? 3 : (I0 ? 4 : 1)) k_shade2(Scene
         }
       }
       Bc.seed[item] = seed;
+    }
+    if constexpr (!I0) {  // only the mask lived across the NEE block: the live rays' slots, the dead ones counted
+      const uint32_t nl = (uint32_t)__popc(live);
+      s0 = block_append_skip(shcnt, nl, qcounter(B.ctr, B.lslot, 1, sub), dead_total(S), nr - nl, sm);
+      queue_live(shq, s0, kind, live, item);
     }
     if constexpr (EXT) {  // the area-light shadow rays of the block, one more append
       const uint32_t a0 = block_append(shcnt, area_ray ? 1u : 0u, sm);
@@ -669,10 +701,12 @@ __global__ void __launch_bounds__(kBlock, I0 ? 4 : 1) k_shade2m(SceneDev S, Trac
           if (cached) lvis_split(lv, kind, ask, vis0);
         }
       }
-      // the block's shadow-ray slots, one atomic per pass (I0, pass 0: of the rays not known yet, k_shade2)
-      const uint32_t s0 = cached ? block_append_skip(shcnt, (uint32_t)__popc(ask), qcounter(B.ctr, B.lslot, 1, sub),
-                                                     lvis_total(S), nr - (uint32_t)__popc(ask), sm)
-                                 : block_append(shcnt, nr, sm);
+      // the block's shadow-ray slots, one atomic per pass (I0, pass 0: of the rays not known yet, k_shade2; else
+      // behind the NEE block, of the live rays)
+      uint32_t s0 = 0, live = 0;
+      if (cached)
+        s0 = block_append_skip(shcnt, (uint32_t)__popc(ask), qcounter(B.ctr, B.lslot, 1, sub), lvis_total(S),
+                               nr - (uint32_t)__popc(ask), sm);
       uint32_t status = kStMiss, emissive = 0;
       if (nr) {
         const float4 o = rop[item], d = rdp[item];
@@ -681,16 +715,13 @@ __global__ void __launch_bounds__(kBlock, I0 ? 4 : 1) k_shade2m(SceneDev S, Trac
         const V3 I = v3(o.x, o.y, o.z) + hh.x * D;                                           // tiny_bvh.h:586
         const V3 V = -D;
         const HitAttr ha = hit_attributes(Sc, hit_inst(Sc, pk), hit_prim(Sc, pk), hh.y, hh.z, (fl & kNormalMap) != 0);
-        Bc.hp[sn] = make_float4(I.x, I.y, I.z, 0.0f);
         float4 nk;
         const V3 brdf = nee_lights(Sc, fl, kind, I, V, ha.N, ha.m, seed, nk, [&](int k, uint32_t light) {
-          if (cached) {
-            if (ask & (1u << (8 * k)))
-              shq[s0 + (uint32_t)__popc(ask & ((1u << (8 * k)) - 1u))] = (light << 29) | (4u * (uint32_t)sn + (uint32_t)k);
-          } else {
-            shq[s0 + k] = (light << 29) | (4u * (uint32_t)sn + (uint32_t)k);
-          }
+          if (cached && (ask & (1u << (8 * k))))
+            shq[s0 + (uint32_t)__popc(ask & ((1u << (8 * k)) - 1u))] = (light << 29) | (4u * (uint32_t)sn + (uint32_t)k);
         });
+        if (!cached) live = Bc.dead ? nee_live(Sc, fl, kind, nk) : (1u << nr) - 1u;  // (k_shade2)
+        if (cached || live) Bc.hp[sn] = make_float4(I.x, I.y, I.z, 0.0f);
         const V3 e = v3(0.0f, 0.0f, 0.0f) + v3(1.0f, 1.0f, 1.0f) * ha.m.emis;                // :196
         if (e.x != 0.0f || e.y != 0.0f || e.z != 0.0f) {
           Bc.ne[sn] = make_float4(e.x, e.y, e.z, 0.0f);
@@ -713,6 +744,11 @@ __global__ void __launch_bounds__(kBlock, I0 ? 4 : 1) k_shade2m(SceneDev S, Trac
           }
         }
         Bc.seed[item] = seed;
+      }
+      if (!cached) {  // the live rays' slots; the dead ones counted (k_shade2)
+        const uint32_t nl = (uint32_t)__popc(live);
+        s0 = block_append_skip(shcnt, nl, qcounter(B.ctr, B.lslot, 1, sub), dead_total(S), nr - nl, sm);
+        queue_live(shq, s0, kind, live, (uint32_t)sn);
       }
       if (act) {
         Bc.rinfo[sn] = depth | (path << 8) | (status << 16) | ((uint32_t)kind << 20) | emissive | kRiFresh |

@@ -385,6 +385,16 @@ class Context:
         check(self.L.prt_shadow_reuse(self.h, C.byref(n), 1 if reset else 0))
         return int(n.value)
 
+    def shadow_dead(self, reset=False):
+        """Shadow rays the calls so far counted instead of tracing because their contribution is exactly zero: the
+        light behind the shading normal, the hit outside the spot's cone, a black light, PRT_FLAG_LIGHTED off
+        (prt_shadow_dead).  Counted on the device: waits for the queued frames, like ray_totals.  0 in the debug
+        render modes and with PRT_DEAD_SHADOW=0; an area light's own ray is never counted; rays under the light-visibility record count in
+        shadow_reuse() instead."""
+        n = C.c_uint64()
+        check(self.L.prt_shadow_dead(self.h, C.byref(n), 1 if reset else 0))
+        return int(n.value)
+
     def save_accumulation(self) -> bytes:
         """The accumulation state (accumulator, samplesPerPixel, distances) as an opaque blob
         (prt_save_accumulation); b"" before the first render."""
