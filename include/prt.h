@@ -261,9 +261,12 @@ int prt_shadow_reuse(prt_ctx* ctx, uint64_t* reused, int32_t reset);
 /* Dead shadow-ray counter (additive within ABI 10).  A next-event shadow ray is dead when the factor its visibility
  * answer is multiplied by is exactly zero: PRT_FLAG_LIGHTED is off, or every channel of its unoccluded contribution
  * compares equal to zero (the light is behind the shading normal, the hit point is outside the spot's cone, the
- * light is black).  Renders count such rays of the point, directional and spot lights instead of tracing them
- * (bit-identical images; PRT_DEAD_SHADOW=0 in the environment traces them all; the debug render modes cast no
- * shadow rays, and an area light's own ray is traced as ever).  Rays under the light-visibility record
+ * light is black), or the one BRDF value all the item's rays are multiplied by is zero in every channel (the shading
+ * normal faces away from the viewer or from the light the BRDF is evaluated for) while their contributions are
+ * bounded.  Renders count such rays of the point, directional and spot lights instead of tracing them
+ * (bit-identical images; PRT_DEAD_SHADOW in the environment is a level: 0 traces them all, 1 leaves the BRDF rule
+ * out, unset or anything else applies both; the debug render modes cast no shadow rays, and an area light's own ray
+ * is traced as ever).  Rays under the light-visibility record
  * (prt_shadow_reuse) are asked, learned and counted there as before.  dead: the shadow rays skipped this way so
  * far, counted on the device; waits like prt_shadow_reuse (a local group: summed over its members); reset != 0
  * zeroes it after reading.  A dead shadow ray is still a shadow ray of its path: prt_ray_totals and prt_stats count

@@ -946,11 +946,14 @@ bool shadow_reuse_on() {
   return !(e && std::atoi(e) == 0);
 }
 // Dead shadow rays (prt_wave2.hip nee_live) are counted instead of traced by every shading kernel of render mode 0,
-// outside the rays the light-visibility record answers for; PRT_DEAD_SHADOW=0 traces them all (A/B runs, tests).
-// Read per call
-bool dead_shadow_on() {
+// outside the rays the light-visibility record answers for.  PRT_DEAD_SHADOW is a level (A/B runs, tests): 0 traces
+// them all, 1 skips only the rays whose own contribution is zero, unset or anything else (2) also every ray of an item
+// whose BRDF value is zero.  Read per call
+uint32_t dead_shadow_level() {
   const char* e = std::getenv("PRT_DEAD_SHADOW");
-  return !(e && std::atoi(e) == 0);
+  if (!e) return 2u;
+  const int v = std::atoi(e);
+  return v == 0 ? 0u : (v == 1 ? 1u : 2u);
 }
 // the key of the primary hits a call with scene S and tile map M would trace
 PrimKey prim_key(const prt_ctx* c, const SceneDev& S, const TileMap& M) {
@@ -1114,7 +1117,7 @@ int enqueue_render_body(prt_ctx* c, const prt_render_params* p, const TileMap& M
     ws0.wb.pmode = kPrimTrace;
     ws0.wb.lvis = nullptr;
     ws0.wb.lslot = iters + 1;
-    ws0.wb.dead = dead_shadow_on() ? 1u : 0u;
+    ws0.wb.dead = dead_shadow_level();
     if (R.preuse && nb > 0) {
       const PrimKey key = prim_key(c, S, M);
       const uint64_t px = tile_image_pixels(M);  // the tile map's entries that have a pixel (and a ray)

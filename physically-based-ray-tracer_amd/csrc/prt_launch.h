@@ -81,8 +81,9 @@ struct WaveBufs {
   uint2* lvis;
   uint32_t lslot;          // the iteration whose shadow counter counts the shadow rays not queued (iters + 1): those
                            // answered from lvis and the dead ones
-  uint32_t dead;           // skip dead shadow rays (prt_wave2.hip; PRT_DEAD_SHADOW=0 clears it).  In the struct's
-                           // tail padding: the kernel arguments behind a WaveBufs stay where they were
+  uint32_t dead;           // dead shadow rays (prt_wave2.hip), the PRT_DEAD_SHADOW level: 0 trace them all, 1 skip those
+                           // whose contribution is zero, 2 (default) also those a zero BRDF value multiplies.  In the
+                           // struct's tail padding: the kernel arguments behind a WaveBufs stay where they were
 };
 static_assert(sizeof(WaveBufs) % 8 == 0 && offsetof(WaveBufs, dead) + 4 == sizeof(WaveBufs),
               "dead fills WaveBufs' tail padding");

@@ -148,15 +148,36 @@ __device__ __forceinline__ V3 nee_contrib(const SceneDev& S, int kind, int k, fl
 // outside the spot's cone, an underflow, a black light): nee_resolve then adds colour x 0, or nothing, to a sum
 // that starts at +0 and is never -0, so the ray's answer cannot change a bit of the result.  A NaN compares unequal
 // and stays live.
-__device__ __forceinline__ uint32_t nee_live(const SceneDev& S, uint32_t fl, int kind, float4 nk) {
+// brdf_rule (PRT_DEAD_SHADOW level 2, the default): every ray of the item is dead, too, when every channel of the
+// item's one BRDF value (nee_lights' return: exactly (0,0,0) whenever N.V <= 0 or N.L <= 0 for the light it was
+// evaluated for, prt_shade.h eval_combined_brdf; for the point-light class that is the one drawn light, whatever the
+// four rays' own cosines are) compares equal to zero and every channel of every ray's contribution is at most
+// kDeadMax in magnitude.  nee_resolve computes e + (1,1,1) * (brdf * c), c = the sum of the unoccluded rays'
+// contributions divided by the class probability: with at most four terms of at most 2^120 and a divisor of at
+// least 0.2, |c| <= 2^125 is finite whatever the rays answer, so brdf * c is +0 or -0 in every channel; e is
+// 0 + emissive, never -0, so e + (+-0) == e bit for bit (a NaN e keeps its payload either way).  A NaN or infinite
+// BRDF value compares unequal to zero, and a NaN, infinite or larger contribution fails the bound (0 * inf would
+// make the answers matter): both keep the contribution rule alone.
+constexpr float kDeadMax = 0x1p120f;
+__device__ __forceinline__ uint32_t nee_live(const SceneDev& S, uint32_t fl, int kind, float4 nk, V3 brdf,
+                                             bool brdf_rule) {
   if (!(fl & kLighted)) return 0u;
   const auto nz = [](V3 c) { return !(c.x == 0.0f && c.y == 0.0f && c.z == 0.0f); };
-  if (kind != 0) return nz(nee_contrib(S, kind, 0, nk)) ? 1u : 0u;
+  const auto small = [](V3 c) { return fabsf(c.x) <= kDeadMax && fabsf(c.y) <= kDeadMax && fabsf(c.z) <= kDeadMax; };
+  const bool zero_brdf = brdf_rule && !nz(brdf);
+  if (kind != 0) {
+    const V3 c = nee_contrib(S, kind, 0, nk);
+    return (nz(c) && !(zero_brdf && small(c))) ? 1u : 0u;
+  }
   uint32_t live = 0;
+  bool bounded = true;
 #pragma unroll
-  for (int k = 0; k < 4; k++)
-    if (nz(nee_contrib(S, 0, k, nk))) live |= 1u << k;
-  return live;
+  for (int k = 0; k < 4; k++) {
+    const V3 c = nee_contrib(S, 0, k, nk);
+    if (nz(c)) live |= 1u << k;
+    bounded = bounded && small(c);
+  }
+  return (zero_brdf && bounded) ? 0u : live;
 }
 
 // result after NEE: emissive + throughput(=1) * (BRDF * contribution), the reference's float order.

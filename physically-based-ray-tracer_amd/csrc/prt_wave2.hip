@@ -67,10 +67,15 @@
 // its record; the host clears it (hipMemsetAsync on the state's stream, before k_wave_init) when a dense pass has
 // rewritten phit since it was learned or the light positions differ (prt_api.cpp enqueue_render_body).
 //
-// Dead shadow rays (every shading form but the two under the record above; B.dead, PRT_DEAD_SHADOW=0 clears it).  A
+// Dead shadow rays (every shading form but the two under the record above; B.dead, the PRT_DEAD_SHADOW level).  A
 // light-class shadow ray is dead when its visibility answer is multiplied by exactly zero: PRT_FLAG_LIGHTED is off,
 // or every channel of nee_contrib compares equal to zero (prt_path.h nee_live: the cosine clamped to 0, a hit outside
-// the spot's cone, a black light).  The reference traces such rays; their answer cannot change a bit of the result.
+// the spot's cone, a black light), or (level 2) the item's one BRDF value is zero in every channel while every ray's
+// contribution is bounded: the shading normal faces away from the viewer, or from the light the BRDF was evaluated for
+// (the point-light class multiplies all four rays by the BRDF of the one drawn light), so every ray of the item is
+// moot.  The reference traces such rays; their answer cannot change a bit of the result.  Levels (read per call,
+// wave-uniform): PRT_DEAD_SHADOW=0 traces everything, 1 applies the contribution rule alone, unset or anything else
+// applies both.
 // The shading runs its NEE block first and appends the block's shadow-ray slots behind it: only the live rays are
 // queued, in compact slots, their entries rebuilt from the item's light class and its live mask (queue_live); the
 // dead ones are counted into the shadow counter of iteration iters + 1 (B.lslot, as the rays the record answers) and
@@ -536,7 +541,7 @@ __global__ void __launch_bounds__(kBlock, EXT ? 3 : (I0 ? 4 : 1)) k_shade2(Scene
         }
       });
       // dead rays (!I0): counted, not queued; their visibility bytes keep the "occluded" 0 stored below
-      if constexpr (!I0) live = Bc.dead ? nee_live(Sc, fl, kind, nk) : (1u << nr) - 1u;
+      if constexpr (!I0) live = Bc.dead ? nee_live(Sc, fl, kind, nk, brdf, Bc.dead > 1u) : (1u << nr) - 1u;
       // a shadow ray is queued as (light, visibility index) with the item's hit point I stored once: the traversal
       // kernel rebuilds it (shadow_of, the only reader: an item that queues no light-class ray needs none)
       if (I0 || live) Bc.hp[item] = make_float4(I.x, I.y, I.z, 0.0f);
@@ -720,7 +725,7 @@ __global__ void __launch_bounds__(kBlock, I0 ? 4 : 1) k_shade2m(SceneDev S, Trac
           if (cached && (ask & (1u << (8 * k))))
             shq[s0 + (uint32_t)__popc(ask & ((1u << (8 * k)) - 1u))] = (light << 29) | (4u * (uint32_t)sn + (uint32_t)k);
         });
-        if (!cached) live = Bc.dead ? nee_live(Sc, fl, kind, nk) : (1u << nr) - 1u;  // (k_shade2)
+        if (!cached) live = Bc.dead ? nee_live(Sc, fl, kind, nk, brdf, Bc.dead > 1u) : (1u << nr) - 1u;  // (k_shade2)
         if (cached || live) Bc.hp[sn] = make_float4(I.x, I.y, I.z, 0.0f);
         const V3 e = v3(0.0f, 0.0f, 0.0f) + v3(1.0f, 1.0f, 1.0f) * ha.m.emis;                // :196
         if (e.x != 0.0f || e.y != 0.0f || e.z != 0.0f) {
