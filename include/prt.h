@@ -184,6 +184,29 @@ int prt_finish(prt_ctx* ctx);
 /* ---- scene (Scene / Model / Camera state) ---- */
 int prt_set_textures(prt_ctx* ctx, const prt_texture* textures, int32_t count);
 int prt_set_meshes(prt_ctx* ctx, const prt_mesh* meshes, int32_t count);
+/* In-place mesh update with a BLAS refit (additive in ABI 10).  Mesh mesh_index of the last
+ * prt_set_meshes takes the arrays of *mesh; its BLAS keeps its topology (the nodes, their slots, the order of the
+ * triangle records) and its boxes are refitted bottom-up on the device.  Afterwards every query and render returns,
+ * bit for bit, what a fresh context returns after prt_set_meshes with that mesh replaced by *mesh, whatever builder
+ * made the tree.  tri_count, vertex_count and the four texture ids must equal the mesh's current ones
+ * (PRT_ERR_INVALID_ARGUMENT otherwise, and nothing changes); all six arrays are required.
+ * in_flags = 0: the arrays are host memory; indices is range-checked on the host (nothing changes on failure); the
+ * arrays go through a pinned buffer of the context.  On a local group or RCCL context they apply to every member.
+ * in_flags = PRT_IN_DEVICE: all six arrays are device memory on the context's device (after a skinning kernel, for
+ * example; triangles 16-byte aligned), read in the context stream's order.  The kernels check every index against
+ * vertex_count: one out of range reads vertex 0 in its place (never out of range) and the call returns
+ * PRT_ERR_INVALID_ARGUMENT; THE MESH IS THEN IN A TRAVERSABLE BUT UNSPECIFIED STATE until the next successful
+ * prt_update_mesh of it or prt_set_meshes.
+ * The call waits on the host once, for 28 bytes (the mesh's new box and that flag), after its own kernels.  On a
+ * local group: PRT_ERR_UNSUPPORTED.
+ * Ordering: the call joins the frames in flight and enqueues its work on the context stream: frames enqueued
+ * before it see the old geometry, frames enqueued after it (on any in-flight stream) the new one.  It neither
+ * drains the context nor reallocates: its scratch is sized at the first update after a prt_set_meshes (that one
+ * update also reads the mesh's nodes back once, to order them by tree level) and kept.  The instance boxes and the
+ * instance BVH follow at the next frame, as after prt_set_instances; kept primary hits and light visibility go
+ * stale.  No scene: PRT_ERR_NOT_READY.  A NaN coordinate is ignored by the boxes, as the builders ignore it. */
+#define PRT_IN_DEVICE (1u << 0)
+int prt_update_mesh(prt_ctx* ctx, int32_t mesh_index, const prt_mesh* mesh, uint32_t in_flags);
 /* transforms: 16*count floats, row-major BLASInstance::transform; mesh_index: count.  Above 64 instances the rays
  * walk an instance BVH, rebuilt for every call as the reference's per-frame BVH::Build (a host SAH build): on the
  * calling thread when the instance count changes, otherwise on the context's worker thread, the context stream
@@ -609,6 +632,11 @@ typedef struct {
     float   tlas_build_cpu_ms; /* (ABI 10) its thread CPU time */
 } prt_scene_info;
 int prt_get_scene_info(prt_ctx* ctx, prt_scene_info* info);
+/* (additive in ABI 10) The Node8 records of mesh mesh_index's BLAS (80 bytes each, node 0 = the root), for tests and
+ * tools: waits for the context stream and copies them to host memory, child_base and tri_base made relative to the
+ * mesh (the copy does not depend on where the mesh sits in the concatenated arrays).  *needed (optional) receives
+ * the byte count; nodes == NULL only reports it; bytes < *needed: PRT_ERR_INVALID_ARGUMENT. */
+int prt_read_blas(prt_ctx* ctx, int32_t mesh_index, void* nodes, uint64_t bytes, uint64_t* needed);
 
 #ifdef __cplusplus
 }

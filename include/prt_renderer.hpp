@@ -92,6 +92,25 @@ class Scene {
     check(prt_set_area_lights(ctx, areaLights.empty() ? nullptr : areaLights.data(), (int32_t)areaLights.size()));
     check(prt_set_sky(ctx, skyPixels.empty() ? nullptr : skyPixels.data(), skyWidth, skyHeight));
   }
+  // models[index] was deformed in place (same topology): its arrays go to the device and its BLAS is refitted there
+  // (prt_update_mesh); the instance boxes and the instance BVH follow at the next frame
+  void UpdateModel(prt_ctx* ctx, int32_t index) const {
+    const Model& m = models.at((size_t)index);
+    prt_mesh d{};
+    d.tri_count = m.TriCount();
+    d.vertex_count = (int32_t)(m.vertices.size() / 3);
+    d.triangles = m.triangles.data();
+    d.fixed_normals = m.fixedNormals.data();
+    d.fixed_uvs = m.fixedTextureCoords.data();
+    d.indices = m.indices.data();
+    d.vertices = m.vertices.data();
+    d.face_normals = m.faceNormals.data();
+    d.albedo_tex = m.albedoTexture;
+    d.normal_tex = m.normalTexture;
+    d.metalness_tex = m.metalnessTexture;
+    d.emission_tex = m.emissionTexture;
+    check(prt_update_mesh(ctx, index, &d, 0));
+  }
   // GameObject::Synchronise moved an instance: new transforms, TLAS rebuilt (Core/Renderer.cpp:33-41)
   void UploadInstances(prt_ctx* ctx) const {
     std::vector<float> xf;
@@ -256,6 +275,13 @@ class Renderer {
   void Finish() { check(prt_finish(ctx_)); }  // the frames in flight joined into the context stream
 
   // Camera::HandleInput returned true: new screen plane, accumulator memset (Core/Renderer.cpp:147)
+  // scene.models[index] was deformed (same topology): the device takes it, the model's BLAS is refitted in place and
+  // the accumulation restarts in full (the accumulated frames, sample counts and distances show the old geometry)
+  void ModelChanged(int32_t index) {
+    scene.UpdateModel(ctx_, index);
+    check(prt_reset_accumulation(ctx_, 1));
+  }
+
   void CameraMoved() {
     const prt_camera c = camera.Plane();
     check(prt_set_camera(ctx_, &c));

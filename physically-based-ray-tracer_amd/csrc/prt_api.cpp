@@ -20,6 +20,8 @@
 #include "../../include/prt.h"
 #include "bvh_build.h"
 #include "bvh_gpu.h"
+#include "prt_blas_refit.h"
+#include "prt_blas_refit_gpu.h"
 #include "prt_denoise.h"
 #include "prt_launch.h"
 #include "prt_motion.h"
@@ -260,6 +262,13 @@ struct MeshHost {
   int depth;
   int64_t nodes, leaves;
   int32_t tris;
+  // prt_update_mesh: the mesh's TriMT records [rec_base, rec_base + recs) (more than tris after spatial splits; its
+  // nodes are [MeshDev::root, + nodes)), its vertex count, and the tree levels of the node pass (empty until the
+  // mesh's first update): level d's nodes are order[level_ends[d - 1] .. level_ends[d]) of the mesh's part of
+  // prt_ctx::rf_order
+  uint32_t rec_base = 0, recs = 0;
+  int32_t verts = 0;
+  std::vector<uint32_t> level_ends;
 };
 
 }  // namespace
@@ -304,6 +313,16 @@ struct prt_ctx {
   size_t stage_bytes = 0;  // the size the pool was last allocated for
   uint32_t* stage_flag = nullptr;      // one coherent pinned word per staging buffer (64-B stride): TlasJob::flag
   uint32_t* stage_flag_dev = nullptr;  // its device address
+  // prt_update_mesh (prt_blas_refit.h), allocated at a context's first update for the scene as it stands and kept:
+  // six floats per node (the uninflated boxes), the nodes of every refitted mesh ordered by tree level, the 28-byte
+  // result (root box, bad-index flag) and its pinned host copy; for host arrays, the six arrays back to back in one
+  // pinned buffer (written again once rf_ev says the previous update's copy has run) and their device copy
+  DevBuf rf_box, rf_order, rf_res, rf_in;
+  RefitResult* rf_res_host = nullptr;
+  void* rf_pin = nullptr;
+  size_t rf_pin_bytes = 0;
+  hipEvent_t rf_ev = nullptr;
+  bool rf_pin_used = false;
   DevBuf spill;  // traversal stack levels beyond the LDS ones (BVHs deeper than 17 levels)
   DevBuf diag;   // SceneDev::diag device counters ([0] traversal stack overflows, cumulative per context)
   // area light (prt_set_area_lights): p0, eu, ev, n, Le, area
@@ -1570,6 +1589,107 @@ int shard_setup(prt_ctx* c, int32_t tile) {
     }                                          \
   } while (0)
 
+// ---- prt_update_mesh: scratch, tree levels, staging (the refit itself: prt_blas_refit.h / prt_blas_refit.hip)
+
+// wait for the context stream (bounded on an RCCL-sharded context, as drain())
+int wait_stream(prt_ctx* c, const char* what) {
+  if (c->sh_kind == 1 && c->comm) return rccl_wait(c, c->stream, what);
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return PRT_OK;
+}
+
+// byte offsets of a mesh's six arrays (prt_mesh order) in the staging buffers of host-array updates
+struct RefitStage {
+  size_t off[6], bytes[6], total;
+};
+RefitStage refit_stage(size_t T, size_t V) {
+  RefitStage r;
+  const size_t b[6] = {48 * T, 48 * T, 24 * T, 12 * T, 12 * V, 12 * T};
+  size_t at = 0;
+  for (int k = 0; k < 6; k++) {
+    r.off[k] = at;
+    r.bytes[k] = b[k];
+    at += (b[k] + 255) & ~size_t(255);
+  }
+  r.total = at;
+  return r;
+}
+
+// The scratch of the scene as it stands, allocated by the first update after a prt_set_meshes (which drained the
+// context, so nothing queued reads what a larger allocation replaces) and kept: later updates allocate nothing.
+int refit_scratch(prt_ctx* c, bool host_arrays) {
+  size_t nodes = 0, stage = 0;
+  for (const MeshHost& m : c->mesh_info) {
+    nodes += (size_t)m.nodes;
+    stage = std::max(stage, refit_stage((size_t)m.tris, (size_t)m.verts).total);
+  }
+  HIP_TRY(c->rf_box.ensure(24 * nodes));
+  HIP_TRY(c->rf_order.ensure(4 * nodes));
+  HIP_TRY(c->rf_res.ensure(sizeof(RefitResult)));
+  if (!c->rf_res_host)
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->rf_res_host), sizeof(RefitResult), hipHostMallocDefault));
+  if (!c->rf_ev) HIP_TRY(hipEventCreateWithFlags(&c->rf_ev, hipEventDisableTiming));
+  if (host_arrays) {
+    HIP_TRY(c->rf_in.ensure(stage));
+    if (c->rf_pin_bytes < stage) {
+      if (c->rf_pin_used) HIP_TRY(hipEventSynchronize(c->rf_ev));
+      c->rf_pin_used = false;
+      if (c->rf_pin) HIP_TRY(hipHostFree(c->rf_pin));
+      c->rf_pin = nullptr;
+      c->rf_pin_bytes = 0;
+      HIP_TRY(hipHostMalloc(&c->rf_pin, stage, hipHostMallocDefault));
+      c->rf_pin_bytes = stage;
+    }
+  }
+  return PRT_OK;
+}
+
+// The tree levels of mesh mi, once: its nodes are read back, every link is checked (an interior child after its
+// parent and inside the mesh's nodes, a leaf slot's records inside the mesh's records), and the nodes ordered by
+// level go to the mesh's part of rf_order.  The node pass then runs one launch per level, deepest first.
+int refit_levels(prt_ctx* c, int32_t mi) {
+  MeshHost& mh = c->mesh_info[mi];
+  if (!mh.level_ends.empty()) return PRT_OK;
+  const uint32_t root = c->mesh_host[mi].root;
+  const size_t n = (size_t)mh.nodes;
+  std::vector<Node8> nd(n);
+  HIP_TRY(hipMemcpyAsync(nd.data(), c->nodes8.as<Node8>() + root, n * sizeof(Node8), hipMemcpyDeviceToHost, c->stream));
+  int rc = wait_stream(c, "reading the mesh's BLAS");
+  if (rc) return rc;
+  std::vector<uint32_t> level(n, 0);
+  uint32_t depth = 1;
+  for (size_t j = 0; j < n; j++) {
+    uint32_t child = nd[j].child_base;
+    for (int s = 0; s < 8; s++) {
+      if ((nd[j].imask >> s) & 1u) {
+        const uint64_t l = (uint64_t)child++ - root;
+        if (child <= root || l <= j || l >= n) return fail(PRT_ERR_HIP, "BLAS refit: an interior child is not below its parent");
+        level[l] = level[j] + 1;
+        depth = std::max(depth, level[l] + 1);
+      } else if (nd[j].meta[s]) {
+        const uint64_t first = (uint64_t)nd[j].tri_base + (nd[j].meta[s] >> 3), cnt = nd[j].meta[s] & 7u;
+        if (first < mh.rec_base || first + cnt > (uint64_t)mh.rec_base + mh.recs)
+          return fail(PRT_ERR_HIP, "BLAS refit: a leaf slot's records lie outside the mesh");
+      }
+    }
+  }
+  std::vector<uint32_t> ends(depth, 0), order(n);
+  for (size_t j = 0; j < n; j++) ends[level[j]]++;
+  uint32_t at = 0;
+  std::vector<uint32_t> next(depth);
+  for (uint32_t d = 0; d < depth; d++) {
+    next[d] = at;
+    at += ends[d];
+    ends[d] = at;
+  }
+  for (size_t j = 0; j < n; j++) order[next[level[j]]++] = root + (uint32_t)j;
+  HIP_TRY(hipMemcpyAsync(c->rf_order.as<uint32_t>() + root, order.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+  rc = wait_stream(c, "uploading the mesh's tree levels");
+  if (rc) return rc;
+  mh.level_ends = std::move(ends);
+  return PRT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1656,6 +1776,9 @@ int prt_destroy(prt_ctx* c) {
   c->tlas_worker.reset();  // every job is done: each one's stream wait ran before the synchronisations above
   for (InstSet& I : c->isets)
     for (auto& u : I.uses) (void)hipEventDestroy(u.second);
+  if (c->rf_ev) (void)hipEventDestroy(c->rf_ev);
+  if (c->rf_pin) (void)hipHostFree(c->rf_pin);
+  if (c->rf_res_host) (void)hipHostFree(c->rf_res_host);
   if (c->stage_flag) (void)hipHostFree(c->stage_flag);
   for (StageSlot& st : c->stage) {  // the pinned upload ring (its copies ran: the streams are synchronised)
     if (st.ev) (void)hipEventDestroy(st.ev);
@@ -1845,6 +1968,9 @@ int prt_set_meshes(prt_ctx* c, const prt_mesh* m_in, int32_t n) {
     info[i].nodes = nnodes;
     info[i].leaves = nleaves;
     info[i].tris = M.tri_count;
+    info[i].rec_base = tri_base;
+    info[i].recs = gpu ? gm[i].gi.tris : (uint32_t)(tris.size() - tri_base);
+    info[i].verts = M.vertex_count;
     maxd = std::max(maxd, depth);
   }
   c->nodes8.release();
@@ -1879,6 +2005,123 @@ int prt_set_meshes(prt_ctx* c, const prt_mesh* m_in, int32_t n) {
   c->tlas_dirty = true;
   c->scene_epoch++;  // new geometry and BLASes (and prim bits of the hit word): kept primary hits are stale
   PRT_FOR_MEMBERS(prt_set_meshes(m, m_in, n));
+  return PRT_OK;
+}
+
+int prt_update_mesh(prt_ctx* c, int32_t mi, const prt_mesh* M, uint32_t in_flags) {
+  if (!c || !M) return fail(PRT_ERR_INVALID_ARGUMENT, "bad arguments");
+  if (in_flags & ~PRT_IN_DEVICE) return fail(PRT_ERR_INVALID_ARGUMENT, "unknown input flags");
+  if (c->mesh_host.empty()) return fail(PRT_ERR_NOT_READY, "no meshes: call prt_set_meshes");
+  if (mi < 0 || (size_t)mi >= c->mesh_host.size()) return fail(PRT_ERR_INVALID_ARGUMENT, "mesh index out of range");
+  const bool dev_in = (in_flags & PRT_IN_DEVICE) != 0;
+  if (dev_in && c->sh_kind == 2) return fail(PRT_ERR_UNSUPPORTED, "device arrays on a local shard group");
+  if (!M->triangles || !M->fixed_normals || !M->fixed_uvs || !M->indices || !M->vertices || !M->face_normals)
+    return fail(PRT_ERR_INVALID_ARGUMENT, "mesh update: missing arrays");
+  const MeshDev& md = c->mesh_host[mi];
+  {
+    const MeshHost& mh = c->mesh_info[mi];
+    const int32_t tx[4] = {M->albedo_tex, M->normal_tex, M->metalness_tex, M->emission_tex};
+    if (M->tri_count != mh.tris || M->vertex_count != mh.verts)
+      return fail(PRT_ERR_INVALID_ARGUMENT, "mesh update: the triangle and vertex counts must stay (topology changes need prt_set_meshes)");
+    for (int k = 0; k < 4; k++)
+      if (tx[k] != md.tex[k]) return fail(PRT_ERR_INVALID_ARGUMENT, "mesh update: the texture ids must stay");
+  }
+  const size_t T = (size_t)M->tri_count, V = (size_t)M->vertex_count;
+  if (!dev_in)
+    for (size_t k = 0; k < 3 * T; k++)
+      if (M->indices[k] < 0 || M->indices[k] >= M->vertex_count) return fail(PRT_ERR_INVALID_ARGUMENT, "index out of range");
+  PRT_JOIN(c);  // frames in flight complete first: they read the geometry this call rewrites in place
+  HIP_TRY(hipSetDevice(c->device));
+  int rc = refit_scratch(c, !dev_in);
+  if (rc) return rc;
+  rc = refit_levels(c, mi);
+  if (rc) return rc;
+  MeshHost& mh = c->mesh_info[mi];
+  RefitMeshDev d;
+  d.tri_count = M->tri_count;
+  d.vertex_count = M->vertex_count;
+  const void* src[6] = {M->triangles, M->fixed_normals, M->fixed_uvs, M->indices, M->vertices, M->face_normals};
+  if (!dev_in) {  // through the context's pinned buffer, one copy
+    const RefitStage st = refit_stage(T, V);
+    if (c->rf_pin_used) HIP_TRY(hipEventSynchronize(c->rf_ev));  // the previous update's copy out of it has run
+    c->rf_pin_used = false;
+    char* pin = static_cast<char*>(c->rf_pin);
+    for (int k = 0; k < 6; k++) std::memcpy(pin + st.off[k], src[k], st.bytes[k]);
+    HIP_TRY(hipMemcpyAsync(c->rf_in.p, pin, st.total, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipEventRecord(c->rf_ev, c->stream));
+    c->rf_pin_used = true;
+    for (int k = 0; k < 6; k++) src[k] = c->rf_in.as<char>() + st.off[k];
+  }
+  d.triangles = static_cast<const float*>(src[0]);
+  d.fixed_normals = static_cast<const float*>(src[1]);
+  d.fixed_uvs = static_cast<const float*>(src[2]);
+  d.indices = static_cast<const int32_t*>(src[3]);
+  d.vertices = static_cast<const float*>(src[4]);
+  d.face_normals = static_cast<const float*>(src[5]);
+  RefitResult* res = c->rf_res.as<RefitResult>();
+  HIP_TRY(hipMemsetAsync(&res->bad_index, 0, 4, c->stream));
+  HIP_TRY(launch_refit_records(c->stream, c->tris.as<TriMT>() + mh.rec_base, mh.recs, c->stri.as<ShadeTri>() + md.prim_base, d,
+                               res));
+  for (size_t lv = mh.level_ends.size(); lv-- > 0;) {  // deepest level first; the root last
+    const uint32_t b = lv ? mh.level_ends[lv - 1] : 0u;
+    HIP_TRY(launch_refit_level(c->stream, c->nodes8.as<Node8>(), c->tris.as<TriMT>(), d.triangles, c->rf_box.as<float>(),
+                               c->rf_order.as<uint32_t>() + md.root + b, mh.level_ends[lv] - b, md.root, res));
+  }
+  // the mesh's new box, which the instance records and the instance BVH (built on the host) start from
+  float bmin[3], bmax[3];
+  bool bad = false;
+  if (dev_in) {  // the root box and the bad-index flag, 28 bytes: the call's only host wait
+    HIP_TRY(hipMemcpyAsync(c->rf_res_host, res, sizeof(RefitResult), hipMemcpyDeviceToHost, c->stream));
+    rc = wait_stream(c, "reading the updated mesh's box");
+    if (rc) return rc;
+    std::memcpy(bmin, c->rf_res_host->bmin, sizeof(bmin));
+    std::memcpy(bmax, c->rf_res_host->bmax, sizeof(bmax));
+    bad = c->rf_res_host->bad_index != 0;
+  } else {
+    refit_box_reset(bmin, bmax);
+    for (size_t p = 0; p < T; p++) {
+      const float* a = M->triangles + 12 * p;
+      float lo[3], hi[3];
+      refit_box_reset(lo, hi);
+      refit_box_grow(lo, hi, a);
+      refit_box_grow(lo, hi, a + 4);
+      refit_box_grow(lo, hi, a + 8);
+      refit_box_merge(bmin, bmax, lo, hi);
+    }
+  }
+  std::memcpy(mh.bmin, bmin, sizeof(bmin));
+  std::memcpy(mh.bmax, bmax, sizeof(bmax));
+  c->inst_dirty = true;
+  c->tlas_dirty = true;
+  c->scene_epoch++;  // new geometry: kept primary hits and light visibility are stale
+  if (bad) return fail(PRT_ERR_INVALID_ARGUMENT, "mesh update: an index in device memory is out of range (vertex 0 was read in its place)");
+  PRT_FOR_MEMBERS(prt_update_mesh(m, mi, M, in_flags));
+  return PRT_OK;
+}
+
+int prt_read_blas(prt_ctx* c, int32_t mi, void* nodes, uint64_t bytes, uint64_t* needed) {
+  if (!c) return fail(PRT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  if (c->mesh_host.empty()) return fail(PRT_ERR_NOT_READY, "no meshes: call prt_set_meshes");
+  if (mi < 0 || (size_t)mi >= c->mesh_host.size()) return fail(PRT_ERR_INVALID_ARGUMENT, "mesh index out of range");
+  const MeshHost& mh = c->mesh_info[mi];
+  const uint64_t need = (uint64_t)mh.nodes * sizeof(Node8);
+  if (needed) *needed = need;
+  if (!nodes) return PRT_OK;
+  if (bytes < need) return fail(PRT_ERR_INVALID_ARGUMENT, "prt_read_blas: buffer too small");
+  PRT_JOIN(c);
+  HIP_TRY(hipSetDevice(c->device));
+  const uint32_t root = c->mesh_host[mi].root;
+  HIP_TRY(hipMemcpyAsync(nodes, c->nodes8.as<Node8>() + root, need, hipMemcpyDeviceToHost, c->stream));
+  const int rc = wait_stream(c, "prt_read_blas");
+  if (rc) return rc;
+  Node8* nd = static_cast<Node8*>(nodes);  // offsets relative to the mesh, as the builders return them
+  for (int64_t j = 0; j < mh.nodes; j++) {
+    Node8 x;
+    std::memcpy(&x, nd + j, sizeof(x));
+    x.child_base -= root;
+    x.tri_base -= mh.rec_base;
+    std::memcpy(nd + j, &x, sizeof(x));
+  }
   return PRT_OK;
 }
 

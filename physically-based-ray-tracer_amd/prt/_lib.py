@@ -14,6 +14,7 @@ ABI_VERSION = 10  # PRT_ABI_VERSION of the include/prt.h these structs mirror
 FLAG_AA, FLAG_ACCUMULATE, FLAG_GAMMA, FLAG_NORMALMAP, FLAG_SKYBOX, FLAG_LIGHTED, FLAG_STOCHASTIC = (1 << i for i in range(7))
 FLAGS_DEFAULT = 0x7F
 OUT_DEVICE = 1
+IN_DEVICE = 1  # prt_update_mesh: the mesh's arrays are device memory
 OUT_TIMED = 2  # prt_render_aov / prt_denoise: record the per-pass HIP events prt_denoise_timings reads
 DENOISE_TIMINGS = 10
 BUILDER_HOST_SAH, BUILDER_GPU_LBVH, BUILDER_HOST_SBVH, BUILDER_GPU_PLOC = 0, 1, 2, 3
@@ -36,6 +37,7 @@ EXPORTS = [
     "prt_shadow_dead",
     "prt_render_aov_ids", "prt_instance_motion", "prt_reproject_motion",
     "prt_temporal_defaults", "prt_reproject_moments", "prt_denoise_variance_defaults", "prt_denoise_variance",
+    "prt_update_mesh", "prt_read_blas",
 ]
 SHARD_ID_BYTES = 128
 SHARD_NONE, SHARD_RCCL, SHARD_GROUP = 0, 1, 2  # prt_shard_info.transport
@@ -168,6 +170,8 @@ def load():
         "prt_finish": ([vp], C.c_int),
         "prt_set_textures": ([vp, C.POINTER(Texture), i32], C.c_int),
         "prt_set_meshes": ([vp, C.POINTER(Mesh), i32], C.c_int),
+        "prt_update_mesh": ([vp, i32, C.POINTER(Mesh), u32], C.c_int),
+        "prt_read_blas": ([vp, i32, vp, C.c_uint64, C.POINTER(C.c_uint64)], C.c_int),
         "prt_set_instances": ([vp, vp, vp, i32], C.c_int),
         "prt_set_lights": ([vp, C.POINTER(Lights)], C.c_int),
         "prt_set_sky": ([vp, vp, i32, i32], C.c_int),

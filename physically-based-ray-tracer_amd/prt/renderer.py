@@ -183,6 +183,14 @@ class Scene:
     def tri_count(self):
         return sum(self.models[m].tri_count for m, _ in self.blases)
 
+    def update_model(self, index, mesh):
+        """Model `index` takes `mesh` (a scenes.Mesh of the same topology); hand it to a context with
+        Context.update_mesh(index, mesh), or use Renderer.UpdateModel, which does both."""
+        old = self.models[index]
+        if mesh.tri_count != old.tri_count or np.asarray(mesh.vertices).size != np.asarray(old.vertices).size:
+            raise ValueError("update_model: the triangle and vertex counts must stay (set_scene for a new topology)")
+        self.models[index] = mesh
+
 
 class Context:
     """One prt_ctx on one HIP device (one process per GPU)."""
@@ -299,6 +307,48 @@ class Context:
         xf = _f32(np.stack([T for _, T in blases]).reshape(-1))
         mi = np.ascontiguousarray([m for m, _ in blases], np.uint32)
         check(self.L.prt_set_instances(self.h, xf.ctypes.data, mi.ctypes.data, len(blases)))
+
+    def update_mesh(self, index, mesh, device=False):
+        """prt_update_mesh: mesh `index` of the last set_scene takes `mesh`'s arrays and its BLAS is refitted in place
+        (same triangle and vertex counts, same texture ids; the tree keeps its topology).  `mesh` is a scenes.Mesh of
+        host arrays, or with device=True anything with the same six attributes holding torch tensors on this
+        context's device (float32, indices int32, contiguous) or raw device pointers (ints; then tri_count and
+        vertex_count attributes are required): the arrays are read in the context stream's order, the call waits for
+        28 bytes, and an index out of range raises (the mesh is then traversable but unspecified until the next
+        update)."""
+        names = ("triangles", "fixed_normals", "fixed_uvs", "indices", "vertices", "face_normals")
+        arrs = [getattr(mesh, n) for n in names]
+        if not device:
+            arrs = [np.ascontiguousarray(a, np.int32 if n == "indices" else np.float32) for n, a in zip(names, arrs)]
+            ptrs = [a.ctypes.data for a in arrs]
+            tri_count, verts = arrs[3].size // 3, arrs[4].size // 3
+        else:
+            ptrs = []
+            for n, a in zip(names, arrs):
+                if hasattr(a, "data_ptr"):
+                    want = "torch.int32" if n == "indices" else "torch.float32"
+                    if not a.is_cuda or not a.is_contiguous() or str(a.dtype) != want:
+                        raise ValueError(f"update_mesh: {n} must be a contiguous {want} tensor on the device")
+                    ptrs.append(a.data_ptr())
+                else:
+                    ptrs.append(int(a))
+            tri_count = getattr(mesh, "tri_count", None)
+            verts = getattr(mesh, "vertex_count", None)
+            if tri_count is None:
+                tri_count = arrs[3].numel() // 3
+            if verts is None:
+                verts = arrs[4].numel() // 3
+        m = _lib.Mesh(int(tri_count), int(verts), *ptrs, mesh.albedo, mesh.normal, mesh.metalness, mesh.emission)
+        check(self.L.prt_update_mesh(self.h, int(index), C.byref(m), _lib.IN_DEVICE if device else 0))
+
+    def read_blas(self, index):
+        """prt_read_blas: mesh `index`'s Node8 records as a uint8 array [nodes, 80], child_base / tri_base relative to
+        the mesh (introspection for tests and tools; waits for the context stream)."""
+        n = C.c_uint64()
+        check(self.L.prt_read_blas(self.h, int(index), None, 0, C.byref(n)))
+        buf = np.zeros(n.value, np.uint8)
+        check(self.L.prt_read_blas(self.h, int(index), buf.ctypes.data, n.value, None))
+        return buf.reshape(-1, 80)
 
     def set_materials(self, kinds=None):
         """Per-instance material kinds (_lib.MAT_TEXTURED / MAT_DIELECTRIC / MAT_MIRROR), None = all textured."""
@@ -810,6 +860,15 @@ class Renderer:
             raise ValueError("checkpoint of another image size")
         self.ctx.load_accumulation(z["accumulation"].tobytes())
         self.frame, self.seed = int(z["frame"]), int(z["seed"])
+
+    def UpdateModel(self, index, mesh):
+        """scene.models[index] deformed into `mesh` (same topology): the scene takes it and the context refits the
+        model's BLAS in place (prt_update_mesh; a frame loop: UpdateModel, then scene.blases / TickTemporal(motion=
+        True) or Tick).  The accumulation is reset in full: the accumulated frames, their sample counts and distances
+        show the old geometry."""
+        self.scene.update_model(index, mesh)
+        self.ctx.update_mesh(index, mesh)
+        self.ctx.reset_accumulation(full=True)
 
     def CameraMoved(self):
         """Camera::HandleInput returned true: memset of the accumulator only (Core/Renderer.cpp:147)."""

@@ -1,0 +1,205 @@
+"""The BLAS refit of prt_update_mesh on the CPU (tests/cpp/refit_check.cpp over physically-based-ray-tracer_amd/csrc/
+prt_blas_refit.h, the per-node code the device kernels run, and bvh_build.cpp): a refit with the build's own
+triangles reproduces the host builder's Node8 and TriMT arrays byte for byte; deforming and refitting back does too;
+after a deformation of the order of the mesh's extent every triangle lies inside its slot's decoded box, every slot
+of a child inside the parent's decoded box for that child, and the root's box is the exact bounds; collapsed, huge
+and NaN inputs; the same under AddressSanitizer + UndefinedBehaviorSanitizer as a stand-alone program; the two new
+entry points without a device.  The GPU side: tests/test_gpu_mesh_update.py."""
+import ctypes as C
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import deform
+import degenerate
+import prt
+from prt import _lib, scenes
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "physically-based-ray-tracer_amd", "csrc")
+SRC = [os.path.join(ROOT, "tests", "cpp", "refit_check.cpp"), os.path.join(CSRC, "bvh_build.cpp")]
+SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g", "-O1"]
+SAN_ENV = dict(os.environ, ASAN_OPTIONS="abort_on_error=0:halt_on_error=1:detect_leaks=0",
+               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+
+
+def build_checker(exe, extra=("-O2",)):
+    """tests/cpp/refit_check.cpp, without FMA contraction as the library is built."""
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-ffp-contract=off", *extra, "-I", CSRC, *SRC, "-o", exe],
+                   check=True, capture_output=True, text=True)
+    return exe
+
+
+def run_checker(exe, *args, env=None):
+    r = subprocess.run([exe, *[str(a) for a in args]], capture_output=True, text=True, timeout=300, env=env)
+    assert r.stdout.strip(), r.stderr[-3000:]
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    assert r.returncode == 0 and out["ok"], (out, r.stderr[-2000:])
+    return out
+
+
+def dump_tris(mesh, path):
+    np.ascontiguousarray(mesh.triangles, np.float32).tofile(path)
+    return path
+
+
+def extent(mesh):
+    P = np.asarray(mesh.vertices, np.float64).reshape(-1, 3)
+    return float((P.max(0) - P.min(0)).max())
+
+
+MESHES = {
+    "heightfield": lambda: scenes.config_small(60, 45).meshes[0],
+    "torus": lambda: scenes.torus(40, 20),
+    "deep": lambda: scenes.deep_bvh(1000).meshes[0],
+    "soup": lambda: degenerate.soup_mesh(degenerate.degenerate_soup()[0]),  # duplicates, zero areas, coincident copies
+    "pile": lambda: degenerate.soup_mesh(degenerate.pile()),
+    "zero_area": lambda: degenerate.soup_mesh(degenerate.zero_area()),
+}
+
+
+@pytest.fixture(scope="module")
+def checker(tmp_path_factory):
+    return build_checker(str(tmp_path_factory.mktemp("refit") / "refit_check"))
+
+
+@pytest.fixture(scope="module")
+def files(tmp_path_factory):
+    """{mesh name: (V0 file, V1 file)}: the mesh and its copy under a sine displacement of 0.4 x its extent plus a
+    twist about the vertical axis."""
+    d = tmp_path_factory.mktemp("refit_tris")
+    out = {}
+    for name, make in MESHES.items():
+        m = make()
+        e = extent(m)
+        out[name] = (dump_tris(m, str(d / f"{name}_v0.bin")),
+                     dump_tris(deform.sine_twist(m, amp=0.4 * e, twist=0.6 / max(e, 1e-3) * 5.0), str(d / f"{name}_v1.bin")))
+    return out
+
+
+@pytest.mark.parametrize("spatial", [0, 1])
+@pytest.mark.parametrize("mesh", sorted(MESHES))
+def test_identity_refit_reproduces_the_builder(checker, files, mesh, spatial):
+    """Object splits: byte-identical nodes and records.  The spatial-split builder where it took no split: the same;
+    where it did (its leaf boxes are clipped, the refit's are not): two successive identity refits agree."""
+    out = run_checker(checker, "identity", files[mesh][0], spatial)
+    if not spatial:
+        assert not out["split"]
+    if mesh == "heightfield":
+        assert out["nodes"] > 500 and out["refs"] == 5400
+
+
+@pytest.mark.parametrize("spatial", [0, 1])
+@pytest.mark.parametrize("mesh", sorted(MESHES))
+def test_there_and_back(checker, files, mesh, spatial):
+    out = run_checker(checker, "thereback", files[mesh][0], spatial, files[mesh][1])
+    assert out["moved"]
+
+
+@pytest.mark.parametrize("spatial", [0, 1])
+@pytest.mark.parametrize("mesh", sorted(MESHES))
+def test_containment_after_a_large_deformation(checker, files, mesh, spatial):
+    out = run_checker(checker, "contain", files[mesh][0], spatial, files[mesh][1])
+    P = np.fromfile(files[mesh][1], np.float32).reshape(-1, 4)[:, :3]
+    assert np.array_equal(np.array(out["bmin"], np.float32), P.min(0))
+    assert np.array_equal(np.array(out["bmax"], np.float32), P.max(0))
+    assert out["corners"] >= 9 * len(P) // 3
+
+
+@pytest.mark.parametrize("case", ["point", "huge", "huge_offset"])
+def test_extreme_inputs(checker, files, tmp_path, case):
+    """All vertices collapsed to one point; coordinates of magnitude 1e6; the same far from the origin."""
+    m = MESHES["heightfield"]()
+    P = deform.positions(m)
+    if case == "point":
+        P[:] = (0.25, -1.5, 3.0)
+    elif case == "huge":
+        P *= 2.0e5
+    else:
+        P = P * 0.01 + 1.0e6
+    v1 = dump_tris(deform.with_positions(m, P), str(tmp_path / "v1.bin"))
+    for spatial in (0, 1):
+        run_checker(checker, "contain", files["heightfield"][0], spatial, v1)
+        run_checker(checker, "thereback", files["heightfield"][0], spatial, v1)
+
+
+@pytest.mark.parametrize("mesh,prim", [("heightfield", 0), ("heightfield", 2711), ("torus", 801), ("soup", 500)])
+def test_nan_vertex_is_ignored(checker, files, mesh, prim):
+    """One NaN corner: that triangle's box is the box of its other corners, every node is what it is for the mesh
+    with the corner replaced by another of the triangle's, and only that primitive's records change."""
+    for spatial in (0, 1):
+        out = run_checker(checker, "nan", files[mesh][0], spatial, prim)
+        assert out["records_changed"] >= 1
+
+
+def _libasan():
+    p = subprocess.run(["gcc", "-print-file-name=libasan.so"], capture_output=True, text=True).stdout.strip()
+    return p if os.path.isabs(p) and os.path.exists(p) else None
+
+
+@pytest.mark.skipif(_libasan() is None, reason="gcc's ASan runtime is not installed")
+def test_refit_clean_under_sanitizers(files, tmp_path):
+    """The checker rebuilt with ASan + UBSan and run as a stand-alone program (nothing sanitized is loaded into
+    Python): every mode on the multi-level height field and the degenerate soup, both builders."""
+    exe = build_checker(str(tmp_path / "refit_check_asan"), SAN)
+    for mesh in ("heightfield", "soup", "deep"):
+        v0, v1 = files[mesh]
+        for spatial in (0, 1):
+            run_checker(exe, "identity", v0, spatial, env=SAN_ENV)
+            run_checker(exe, "thereback", v0, spatial, v1, env=SAN_ENV)
+            run_checker(exe, "contain", v0, spatial, v1, env=SAN_ENV)
+            run_checker(exe, "nan", v0, spatial, 3, env=SAN_ENV)
+            run_checker(exe, "hash", v0, spatial, v1, env=SAN_ENV)
+
+
+def test_grid_exponent_is_exact(tmp_path):
+    """refit_grid_exponent against its definition in exact arithmetic: the smallest biased e in 1..254 with
+    255 * 2^(e - 127) >= ext, over powers of two, their neighbours, 255 * 2^k and its neighbours, and random extents."""
+    src = tmp_path / "gexp.cpp"
+    src.write_text('#include <cstdio>\n#include <cstdlib>\n#include "prt_blas_refit.h"\n'
+                   'int main(int c, char** v) { for (int i = 1; i < c; i++) std::printf("%d\\n", '
+                   '(int)prt::refit_grid_exponent(std::strtod(v[i], nullptr))); return 0; }\n')
+    exe = str(tmp_path / "gexp")
+    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-I", CSRC, str(src), "-o", exe], check=True,
+                   capture_output=True, text=True)
+    from fractions import Fraction
+    xs = [0.0, -1.0, 5e-324, 2.0 ** -1022]
+    for k in range(-140, 141, 7):
+        for base in (2.0 ** k, 255.0 * 2.0 ** k):
+            xs += [base, np.nextafter(base, 0.0), np.nextafter(base, np.inf)]
+    xs += list(np.random.default_rng(3).uniform(0, 1, 64) * 2.0 ** np.random.default_rng(4).integers(-130, 130, 64))
+    xs += [1e300, float("inf")]
+    got = [int(l) for l in subprocess.run([exe, *[float(x).hex() for x in xs]], check=True, capture_output=True,
+                                          text=True).stdout.split()]
+
+    def want(x):
+        if not x > 0:
+            return 1
+        if x == float("inf"):
+            return 254
+        e = 1
+        while e < 254 and 255 * Fraction(2) ** (e - 127) < Fraction(x):
+            e += 1
+        return e
+
+    assert got == [want(float(x)) for x in xs]
+
+
+def test_update_mesh_abi_without_a_device():
+    """Both symbols are exported with the header's signatures, and refuse a NULL context (no device needed)."""
+    L = prt.load()
+    assert hasattr(L, "prt_update_mesh") and hasattr(L, "prt_read_blas")
+    assert {"prt_update_mesh", "prt_read_blas"} <= set(_lib.EXPORTS)
+    hdr = open(os.path.join(ROOT, "include", "prt.h")).read()
+    assert "#define PRT_IN_DEVICE (1u << 0)" in hdr and _lib.IN_DEVICE == 1
+    assert "int prt_update_mesh(prt_ctx* ctx, int32_t mesh_index, const prt_mesh* mesh, uint32_t in_flags);" in hdr
+    assert "int prt_read_blas(prt_ctx* ctx, int32_t mesh_index, void* nodes, uint64_t bytes, uint64_t* needed);" in hdr
+    m = _lib.Mesh()
+    assert L.prt_update_mesh(None, 0, C.byref(m), 0) == -1
+    assert L.prt_update_mesh(None, 0, None, _lib.IN_DEVICE) == -1
+    n = C.c_uint64(7)
+    assert L.prt_read_blas(None, 0, None, 0, C.byref(n)) == -1 and b"NULL" in L.prt_last_error()
+    assert L.prt_abi_version() == 10
