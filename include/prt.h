@@ -144,7 +144,8 @@ typedef struct {
     double   ms_trace;      /* device time of the path-tracing kernel(s) only */
     double   ms_closest;    /* device time of the traversal launches (closest + shadow rays together), summed */
     double   ms_anyhit;     /* reserved (0): shadow rays are traced inside the merged traversal launches */
-    int32_t  pipeline;      /* 2 = the merged-trace wavefront (prt_wave2.hip) */
+    int32_t  pipeline;      /* 2 = the merged-trace wavefront (prt_wave2.hip); 3 = the same with each pass's paths
+                               resolved in one launch at its end (prt_defer.hip) */
     int32_t  iterations;    /* traversal launches per call */
     int32_t  batches;       /* 1 */
     int32_t  ranks;         /* shards whose rays these stats count (1 unless a local group summed its members) */

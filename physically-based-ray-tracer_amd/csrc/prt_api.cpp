@@ -102,6 +102,10 @@ struct WaveState {
   WaveBufs wb = {};
   uint32_t n = 0, levels = 0;
   bool ext = false, merge = false;
+  bool hasR = false;  // the (result) stack R is allocated: every pass but one with a deferred resolve needs it
+  // deferred resolve (prt_wave2.hip k_resolve_pass): the record planes, one per wavefront iteration (point_planes);
+  // allocated by the first call that defers on this state
+  DevBuf planes;
   // primary-hit reuse: this state's own copy of the records and the key they were traced under (its stamp)
   DevBuf phit;
   PrimKey pkey = {};
@@ -350,6 +354,7 @@ struct prt_ctx {
   WaveTimers wt = {};
   // the last enqueued render, for its stats (read_stats)
   uint32_t last_iters = 0;
+  bool last_defer = false;  // the last call's passes ran the deferred resolve (prt_stats::pipeline)
   bool last_timers = false;
   uint64_t last_paths = 0;
   uint64_t carry_segments = 0, carry_shadow = 0;  // ray counts of a call's earlier frame passes
@@ -849,11 +854,13 @@ constexpr size_t kCtrWords = (size_t)(kMaxIters + 2) * 2 * (kNSub + 8) * kCtrStr
 // shadow-queue entries one shading launch may append per item: <= 4 light-class + 1 area-light ray; the merged
 // pipeline (no extensions) shades path 1's last segment and path 2's first in the same launch, 4 + 4
 constexpr uint32_t shadow_per_item(bool merge) { return merge ? 8u : 5u; }
-int ensure_wave(WaveState& ws, uint32_t n, int bounces, bool ext, bool merge) {
+// needR: the pass resolves per iteration (every pipeline but the plain one with a deferred resolve) and stacks results
+int ensure_wave(WaveState& ws, uint32_t n, int bounces, bool ext, bool merge, bool needR) {
   const uint32_t levels = (uint32_t)std::max(1, bounces - 1);
   // sub-queue t receives the 256-entry chunks c == t (mod kNSub): at most ceil(ceil(n/256)/kNSub) of them
   const uint32_t qcap = 256u * (((n + 255u) / 256u + kNSub - 1) / kNSub);
-  if (ws.n >= n && ws.levels >= levels && (ws.ext || !ext) && (ws.merge || !merge) && ws.wave.p) {
+  if (ws.n >= n && ws.levels >= levels && (ws.ext || !ext) && (ws.merge || !merge) && (ws.hasR || !needR) &&
+      ws.wave.p) {
     ws.wb.n = n;  // capacity stays; the SoA strides (R/T: depth * n + item) follow the current n
     ws.wb.qcap = qcap;
     ws.wb.scap = shadow_per_item(merge) * qcap;
@@ -866,7 +873,7 @@ int ensure_wave(WaveState& ws, uint32_t n, int bounces, bool ext, bool merge) {
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~size_t(255); return o; };
   const size_t o_seed = take(4ull * n), o_info = take(4ull * n), o_rinfo = take(4ull * ns), o_ro = take(16ull * n),
-               o_rd = take(16ull * n), o_R = take(16ull * ns * levels), o_T = take(16ull * ns * levels),
+               o_rd = take(16ull * n), o_R = needR ? take(16ull * ns * levels) : 0, o_T = take(16ull * ns * levels),
                o_s1 = take(16ull * n), o_jit = take(8ull * n), o_hit = take(16ull * n), o_ne = take(16ull * ns),
                o_nb = take(16ull * ns), o_nk = take(16ull * ns), o_vis = take(merge ? 8ull * n : 5ull * n),
                o_q0 = take(4 * qn), o_q1 = take(4 * qn), o_shq = take(4 * sn), o_hp = take(16ull * ns),
@@ -884,7 +891,7 @@ int ensure_wave(WaveState& ws, uint32_t n, int bounces, bool ext, bool merge) {
   W.qcap = qcap;
   W.scap = shadow_per_item(merge) * qcap;
   W.seed = (uint32_t*)(b + o_seed); W.info = (uint32_t*)(b + o_info); W.rinfo = (uint32_t*)(b + o_rinfo);
-  W.ro = (float4*)(b + o_ro); W.rd = (float4*)(b + o_rd); W.R = (float4*)(b + o_R); W.T = (float4*)(b + o_T);
+  W.ro = (float4*)(b + o_ro); W.rd = (float4*)(b + o_rd); W.R = needR ? (float4*)(b + o_R) : nullptr; W.T = (float4*)(b + o_T);
   W.s1 = (float4*)(b + o_s1); W.jit = (float2*)(b + o_jit); W.hit = (float4*)(b + o_hit);
   W.ne = (float4*)(b + o_ne); W.nb = (float4*)(b + o_nb); W.nk = (float4*)(b + o_nk); W.vis = (uint32_t*)(b + o_vis);
   W.q0 = (uint32_t*)(b + o_q0); W.q1 = (uint32_t*)(b + o_q1); W.shq = (uint32_t*)(b + o_shq); W.hp = (float4*)(b + o_hp);
@@ -899,13 +906,43 @@ int ensure_wave(WaveState& ws, uint32_t n, int bounces, bool ext, bool merge) {
   ws.levels = levels;
   ws.ext = ext;
   ws.merge = merge;
+  ws.hasR = needR;
   return PRT_OK;
+}
+
+// Deferred resolve (prt_wave2.hip k_resolve_pass): the plain pipeline (no extensions, render mode 0, not merged)
+// resolves a pass's paths in one launch behind its last traversal, from record planes the shading of each iteration
+// fills: rinfo, ne, nb, nk, vis and T, 72 bytes per item and iteration.  A pass is deferred when the planes of the
+// call's largest pass fit the budget per wavefront state: PRT_DEFER_BUDGET_MB (MiB, read per call), 4096 by default
+// (the bench's 1920x1080 x 2 frames x 8 iterations take 2279); a call over it runs the per-iteration resolves.
+// PRT_DEFER_RESOLVE=0 switches it off (A/B runs, tests).  Read per call
+size_t plane_bytes(uint32_t n, uint32_t iters) {  // (each array on a 256-byte boundary)
+  const size_t a4 = (4ull * n * iters + 255) & ~size_t(255), a16 = (16ull * n * iters + 255) & ~size_t(255);
+  return 2 * a4 + 4 * a16;
+}
+bool defer_for(const prt_render_params* p, bool ext, bool merge, uint32_t n, uint32_t iters) {
+  if (ext || merge || p->render_mode != 0 || p->bounces <= 0 || n == 0) return false;
+  const char* e = std::getenv("PRT_DEFER_RESOLVE");
+  if (e && std::atoi(e) == 0) return false;
+  const char* b = std::getenv("PRT_DEFER_BUDGET_MB");
+  const uint64_t budget = (b ? std::strtoull(b, nullptr, 10) : 4096ull) << 20;
+  return plane_bytes(n, iters) <= budget;
+}
+// the record pointers of W -> plane 0 of the planes laid out for n items and `iters` iterations (plane i of an array
+// lies i * n entries behind plane 0)
+void point_planes(WaveBufs& W, const DevBuf& planes, uint32_t n, uint32_t iters) {
+  char* b = planes.as<char>();
+  const size_t a4 = (4ull * n * iters + 255) & ~size_t(255), a16 = (16ull * n * iters + 255) & ~size_t(255);
+  W.rinfo = (uint32_t*)b; W.vis = (uint32_t*)(b + a4);
+  W.ne = (float4*)(b + 2 * a4); W.nb = (float4*)(b + 2 * a4 + a16); W.nk = (float4*)(b + 2 * a4 + 2 * a16);
+  W.T = (float4*)(b + 2 * a4 + 3 * a16);
+  W.R = nullptr;
 }
 
 // the context's running ray totals (prt_ray_totals): bytes 16-31 of the diag buffer, zeroed at prt_create
 Counters* ray_totals_dev(prt_ctx* c) { return reinterpret_cast<Counters*>(c->diag.as<char>() + 16); }
 
-// k_shade2 reads its arguments through the kernarg segment (prt_wave2.hip Shade2Args) and flags diag[1] when the
+// k_shade2 reads its arguments through the kernarg segment (prt_shade2.h Shade2Args) and flags diag[1] when the
 // layout it assumes is not the compiler's (it then shades nothing).  Checked once per context, after its first
 // render (one host wait), so stats-less frame loops fail loudly too; prt_ray_totals re-checks it
 int check_layout_once(prt_ctx* c, hipStream_t st) {
@@ -948,6 +985,7 @@ struct RenderPlan {
   bool ext = false, merge = false;
   bool preuse = false;  // primary-hit reuse applies to this call (primary_reuse_for)
   bool lreuse = false;  // ... and the light-visibility record (shadow_reuse_on)
+  bool defer = false;   // the passes' resolves are deferred (defer_for)
   uint32_t iters = 0;
 };
 
@@ -1042,8 +1080,10 @@ int prepare_render(prt_ctx* c, const prt_render_params* p, const TileMap& M, int
     return fail(PRT_ERR_UNSUPPORTED, S.has_diel ? "dielectric path trees exceed the wavefront iteration limit (lower bounces)"
                                                 : "too many wavefront iterations");
   // sized for the first (largest) pass; later passes hold no more items
-  rc = ensure_wave(flight_ws(c, fl), (uint32_t)(per * (uint64_t)F0), p->bounces, ext, merge);
+  const bool defer = defer_for(p, ext, merge, (uint32_t)(per * (uint64_t)F0), iters);
+  rc = ensure_wave(flight_ws(c, fl), (uint32_t)(per * (uint64_t)F0), p->bounces, ext, merge, !defer);
   if (rc) return rc;
+  if (defer) HIP_TRY(flight_ws(c, fl).planes.ensure(plane_bytes((uint32_t)(per * (uint64_t)F0), iters)));
   R.preuse = primary_reuse_for(p, ext) && per > 0 && F > 0;
   if (R.preuse) {  // this chain's copy of the primary hits; a new allocation holds nothing yet
     WaveState& ws = flight_ws(c, fl);
@@ -1058,6 +1098,7 @@ int prepare_render(prt_ctx* c, const prt_render_params* p, const TileMap& M, int
     }
   }
   R.F = F; R.fmax = fmax; R.npass = npass; R.F0 = F0; R.per = per; R.ext = ext; R.merge = merge; R.iters = iters;
+  R.defer = defer;
   return PRT_OK;
 }
 
@@ -1122,7 +1163,7 @@ int enqueue_render_body(prt_ctx* c, const prt_render_params* p, const TileMap& M
     A.frames = Fb;
     const uint64_t nb = per * (uint64_t)Fb;  // this pass's items
     float4* frames = flight_frames(c, fl).as<float4>();
-    rc = ensure_wave(ws0, (uint32_t)nb, p->bounces, ext, R.merge);  // no allocation: prepare_render sized it for pass 0
+    rc = ensure_wave(ws0, (uint32_t)nb, p->bounces, ext, R.merge, !R.defer);  // no allocation: prepare_render sized it for pass 0
     if (rc) return rc;
     ws0.wb.base = 0;
     ws0.wb.coop_tail = coop;
@@ -1176,9 +1217,13 @@ int enqueue_render_body(prt_ctx* c, const prt_render_params* p, const TileMap& M
       HIP_TRY(launch_clear2(Lw, ws0.wb.ctr, (uint32_t)qw, ws0.wb.ctr + fbase, (uint32_t)fw));
     }
     if (ext && S.has_diel) HIP_TRY(hipMemsetAsync(ws0.wb.dst, 0, 4ull * ws0.wb.n, st));
-    HIP_TRY(launch_wave_init(Lw, S, A, M, ws0.wb, frames));
+    // deferred resolve: the launches get the record planes (laid out for this pass's items) in place of the state's
+    // per-item records; k_wave_init clears the status words of plane 0
+    WaveBufs wb = ws0.wb;
+    if (R.defer) point_planes(wb, ws0.planes, (uint32_t)nb, iters);
+    HIP_TRY(launch_wave_init(Lw, S, A, M, wb, frames));
     for (uint32_t it = 0; it <= iters; it++)
-      HIP_TRY(launch_wave2_iter(Lw, S, A, M, ws0.wb, frames, timers ? &c->wt : nullptr, it));
+      HIP_TRY(launch_wave2_iter(Lw, S, A, M, wb, frames, timers ? &c->wt : nullptr, it, R.defer));
     if (ws0.wb.pmode == kPrimDense) ws0.pvalid = true;
     if (last && want_stats) HIP_TRY(hipEventRecord(c->ev[1], st));
     // post-processing (single-GPU image): the screen pass needs the average and, for the aberration, the
@@ -1213,6 +1258,7 @@ int enqueue_render_body(prt_ctx* c, const prt_render_params* p, const TileMap& M
   }
   if (want_stats) HIP_TRY(hipEventRecord(c->ev[2], st));
   c->last_iters = iters;
+  c->last_defer = R.defer;
   c->last_timers = timers;
   c->last_paths = tile_image_pixels(M) * (uint64_t)F * ((p->flags & PRT_FLAG_AA) ? 2u : 1u);
   return check_layout_once(c, st);
@@ -1269,7 +1315,7 @@ int run_render(prt_ctx* c, const prt_render_params* p, const TileMap& M, float4*
 }
 
 // the context's traversal stack overflow count (SceneDev::diag[0]); waits for the context stream.  diag[1] != 0:
-// a kernel found its kernarg layout assumption broken (prt_wave2.hip Shade2Args) and did no work; diag[2] != 0: the
+// a kernel found its kernarg layout assumption broken (prt_shade2.h Shade2Args) and did no work; diag[2] != 0: the
 // stream's wait for a worker build of the instance BVH timed out (k_wait_host)
 uint64_t diag_overflows(prt_ctx* c, bool* layout_ok = nullptr, bool* wait_ok = nullptr) {
   uint32_t v[3] = {0, 0, 0};
@@ -1372,7 +1418,7 @@ int read_stats(prt_ctx* c, prt_stats* stats) {
     if (!wait_ok) return fail(PRT_ERR_HIP, "the stream's wait for an instance-BVH build timed out");
     stats->segments += c->carry_segments;  // earlier passes of a call above 2^30 work items
     stats->shadow_rays += c->carry_shadow;
-    stats->pipeline = 2;
+    stats->pipeline = c->last_defer ? 3 : 2;
     stats->iterations = (int32_t)(iters + 1);  // traversal launches
     stats->batches = 1;
     stats->ranks = 1;
@@ -2352,7 +2398,7 @@ int prt_shadow_reuse(prt_ctx* c, uint64_t* reused, int32_t reset) {
   std::vector<prt_ctx*> all{c};
   all.insert(all.end(), c->members.begin(), c->members.end());
   uint64_t n = 0;
-  for (prt_ctx* m : all) {  // the device's count (prt_wave2.hip lvis_total), 8 bytes behind the ray totals
+  for (prt_ctx* m : all) {  // the device's count (prt_shade2.h lvis_total), 8 bytes behind the ray totals
     HIP_TRY(hipSetDevice(m->device));
     unsigned long long h = 0;
     void* dev = ray_totals_dev(m) + 1;

@@ -111,9 +111,17 @@ struct WaveTimers {
 hipError_t launch_wave_init(const LaunchCfg& c, const SceneDev& S, const TraceArgs& A, const TileMap& M,
                             const WaveBufs& B, float4* out);
 // merged pipeline (prt_wave2.hip): iteration `it` (0..iters) after launch_wave_init -- one traversal launch for
-// P(it) closest + S(it-1) any-hit, then resolve / miss / shade
+// P(it) closest + S(it-1) any-hit, then resolve / miss / shade.
+// defer (plain pipeline only: no extensions, render mode 0, not merged): the pass's resolve is deferred to one launch
+// behind the last traversal (prt_defer.hip k_resolve_pass).  B's rinfo / ne / nb / nk / vis / T then point at plane 0
+// of `iters` record planes of B.n entries each (plane i at i * B.n); B.R is not used
 hipError_t launch_wave2_iter(const LaunchCfg& c, const SceneDev& S, const TraceArgs& A, const TileMap& M,
-                             const WaveBufs& B, float4* out, WaveTimers* tm, uint32_t it);
+                             const WaveBufs& B, float4* out, WaveTimers* tm, uint32_t it, bool defer = false);
+// ... whose shading (into the record plane B points at) and resolve launches prt_defer.hip holds
+void launch_shade2d(hipStream_t s, unsigned grid, const SceneDev& S, const TraceArgs& A, const TileMap& M,
+                    const WaveBufs& B, uint32_t it, bool i0);
+void launch_resolve_pass(hipStream_t s, unsigned grid, const SceneDev& S, const TraceArgs& A, const WaveBufs& B,
+                         uint32_t iters, float4* out, bool learn);
 // zero na words at a and nb words at b (one dispatch)
 hipError_t launch_clear2(const LaunchCfg& c, uint32_t* a, uint32_t na, uint32_t* b, uint32_t nb);
 // acc_prev (nullable): the accumulator state before the last frame of the call (screen-pass input);

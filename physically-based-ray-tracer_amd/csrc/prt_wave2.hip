@@ -28,6 +28,13 @@
 // iteration i-1 before it (misses) or k_shade2(i) (hits) overwrites them; rinfo keeps iteration i-1's status
 // (and whether the item was queued) while info already holds the state of the queued next ray.
 //
+// Deferred resolve (plain pipeline: no extensions, render mode 0, not merged; prt_defer.hip).  Nothing downstream needs
+// a path's radiance before k_accumulate, and an item is shaded in consecutive iterations from 0, so a pass whose record
+// planes fit the budget (prt_api.cpp defer_for) launches no k_res2d: the host hands k_shade2d(i) plane i of rinfo / ne /
+// nb / nk / vis / T (throughput per iteration, not per depth) and k_trace2(i) the vis of plane i - 1, and one
+// k_resolve_pass behind the last traversal launch walks every item's planes bottom-up.  R is not used; the hazards on
+// ne / nb / nk / vis / T above are gone with the shared record; k_trace2 is the same kernel with another pointer.
+//
 // Primary-hit reuse (plain and merged pipeline: no extensions, render mode 0; WaveBufs::phit / pmode).  Path 1 of
 // a pixel starts at the pixel centre (only path 2 is jittered, :61), so its primary ray is the same in every
 // reference frame of a call and in every later call while camera, tile map, scene and instances stay put.  Its
@@ -109,12 +116,6 @@ void lane_stats_dump() {
   (void)hipMemcpyToSymbol(HIP_SYMBOL(g_lane_stats), z, sizeof(z));
 }
 #endif
-
-// The resolve of the plain pipeline (no extensions, render mode 0) and of the merged one walks all items in index
-// order and takes those whose rinfo carries kRiFresh (set by the shading of the last iteration, cleared by the
-// resolve), so its record loads coalesce; with extensions or a debug render mode it walks the last iteration's queue
-// (k_resmiss2), which also shades that iteration's misses
-constexpr uint32_t kResFresh = kRiFresh;
 
 // the merged pipeline's queue of path-2 primaries: the counters of iteration iters + 1 (kind 0), never a path queue
 __device__ __forceinline__ uint32_t q2_iter(const TraceArgs& A) { return 2u * (uint32_t)A.bounces; }
@@ -304,326 +305,9 @@ __global__ void __launch_bounds__(64, WAVES) k_trace2(SceneDev S, WaveBufs B, ui
   if (tl && threadIdx.x == 0) tl[2] = __builtin_amdgcn_s_memrealtime();
 }
 
-// the skybox lookup out of line: its correctly rounded double atan2 / acos would otherwise raise the register
-// budget of the shading kernel, which looks up the sky for its misses itself
-// (the three fields it reads passed by value: a SceneDev& of a kernel argument would copy the struct to scratch)
-__device__ __noinline__ V3 sample_sky_call(const float* sky, int32_t w, int32_t h, V3 D) {
-  SceneDev S{};
-  S.sky = sky;
-  S.skyw = w;
-  S.skyh = h;
-  return sample_sky(S, D);
-}
-
-// ---- misses of P(iter) (:159): sky radiance (or 0) into ne, before k_shade2 replaces the ray.  EXT: a ray
-// that reaches the area light before any geometry ends there (ne = its MIS-weighted radiance, hit = miss).
-template <bool EXT>
-__device__ __forceinline__ void miss_item(const SceneDev& S, const TraceArgs& A, const WaveBufs& B, uint32_t item) {
-  float4 hh = B.hit[item];
-  if constexpr (EXT) {
-    if (S.area) {
-      const float4 o = B.ro[item], d = B.rd[item];
-      const AreaLight AL = area_light(S);
-      float tq, cl;
-      if (area_hit(AL, v3(o.x, o.y, o.z), v3(d.x, d.y, d.z), hh.x, tq, cl)) {
-        const uint32_t depth = B.info[item] & 0xFFu;
-        const float pdf = depth == 0 ? kFar : B.T[(size_t)(depth - 1) * B.n + item].w;
-        const V3 L = area_seen(AL, tq, cl, pdf);
-        B.ne[item] = make_float4(L.x, L.y, L.z, 0.0f);
-        B.hit[item] = make_float4(kFar, 0.0f, 0.0f, 0.0f);
-        return;
-      }
-    }
-  }
-  if (hh.x < kFar) return;
-  V3 L = v3(0.0f, 0.0f, 0.0f);
-  if (A.flags & kSkybox) {
-    const float4 d = B.rd[item];
-    L = sample_sky_call(S.sky, S.skyw, S.skyh, v3(d.x, d.y, d.z));
-  }
-  B.ne[item] = make_float4(L.x, L.y, L.z, 0.0f);
-}
-template <bool EXT>
-__global__ void __launch_bounds__(kBlock) k_miss2(SceneDev S, TraceArgs A, WaveBufs B, uint32_t iter) {
-  __shared__ uint32_t pref[kNSub + 1];
-  const uint32_t* q = (iter & 1) ? B.q1 : B.q0;
-  const uint32_t total = load_prefix(B.ctr, iter, 0, pref);
-  for (uint32_t c = blockIdx.x; c * kBlock < total; c += gridDim.x) {
-    const uint32_t g = c * kBlock + threadIdx.x;
-    if (g >= total) continue;
-    miss_item<EXT>(S, A, B, q[map_slot(pref, g, B.qcap)]);
-  }
-}
-
-// the path of `item` ends at this iteration: with AA and path 1, queue path 2's primary ray (its jitter was
-// drawn at init, :61) -- returns true when a ray was set up for P(iter + 1)
-__device__ __forceinline__ bool start_path2(const SceneDev& S, const TraceArgs& A, const TileMap& M,
-                                            const WaveBufs& B, uint32_t item, uint32_t path) {
-  if (path != 0 || !(A.flags & kAA)) return false;
-  const uint32_t r = (B.base + item) % M.items;
-  int32_t x, y;
-  item_pixel(M, r, x, y);
-  const float2 j = B.jit[item];
-  const Ray r2 = primary_ray(S, (float)x + j.x, (float)y + j.y, A.W, A.H);
-  B.ro[item] = make_float4(r2.O.x, r2.O.y, r2.O.z, 0.0f);
-  B.rd[item] = make_float4(r2.D.x, r2.D.y, r2.D.z, 0.0f);
-  B.info[item] = 1u << 8;
-  return true;
-}
-
-// the sub-path of `item` ends at this iteration (EXT): continue with the refraction ray of the deepest
-// dielectric node whose reflection subtree this was (the reference's depth-first recursion order,
-// Core/Renderer.cpp:346 before :358) -- returns true when a ray was set up for P(iter + 1)
-__device__ __forceinline__ bool diel_next(const WaveBufs& B, uint32_t item, uint32_t depth, uint32_t path) {
-  uint32_t ds = B.dst[item];
-  const uint32_t pend = ds & ~(ds >> 8) & ~(ds >> 24) & 0xFFu & ((1u << depth) - 1u);
-  if (!pend) return false;
-  const uint32_t k = 31u - (uint32_t)__builtin_clz(pend);
-  const float4 o = B.dro[(size_t)k * B.n + item], d = B.drd[(size_t)k * B.n + item];
-  B.ro[item] = make_float4(o.x, o.y, o.z, 0.0f);
-  B.rd[item] = make_float4(d.x, d.y, d.z, 0.0f);
-  B.info[item] = (k + 1u) | (path << 8);
-  B.dst[item] = ds | (1u << (8 + k));
-  return true;
-}
-
-// ---- the light-visibility record (WaveBufs::lvis; header comment).  An entry is 8 bytes, byte l for light l
-// (x: point lights 0-3, y: kLightDir, kLightSpot): 0 unknown, 1 occluded, 2 unoccluded.  Ray k of an item of
-// `kind` goes to light k (kind 0) or to the kind's one light (k = 0).
-static_assert(kBlock <= 256, "block_append_skip packs two counts of up to 4 x kBlock into one word");
-// the bytes of this kind's lights, ray k's in byte k -> ask: bit 8k set where ray k's answer is unknown (it is
-// queued); vis0: byte k = 1 where it is known unoccluded (the visibility word the traversal would have left)
-__device__ __forceinline__ void lvis_split(uint2 e, int kind, uint32_t& ask, uint32_t& vis0) {
-  const uint32_t w = kind == 0 ? e.x : ((kind == 2 ? e.y >> 8 : e.y) & 0xFFu);
-  const uint32_t rays = kind == 0 ? 0x01010101u : 1u;
-  vis0 = (w >> 1) & rays;
-  ask = ~(w | (w >> 1)) & rays;
-}
-// what the asked rays of a kRiLearn item found (its visibility word after the traversal; the bytes of rays that
-// were not asked hold what the record already said) -> the record.  Plain stores: every frame of a pixel that
-// learns writes the same values, and an item of kind 0 writes all four point-light bytes, as one word.
-__device__ __forceinline__ void lvis_learn(const WaveBufs& B, uint32_t item, uint32_t ri) {
-  const uint32_t kind = (ri >> 20) & 3u, vw = B.vis[item];
-  uint2* e = B.lvis + (B.base + item) % B.pitems;
-  if (kind == 0) e->x = 0x01010101u + (vw & 0x01010101u);
-  else reinterpret_cast<uint8_t*>(e)[kind == 2 ? 5 : 4] = (uint8_t)(1u + (vw & 1u));
-}
-// the context's running total of shadow rays answered from the record (prt_shadow_reuse): 8 bytes behind the ray
-// totals in the diagnostics buffer
-__device__ __forceinline__ unsigned long long* lvis_total(const SceneDev& S) {
-  return reinterpret_cast<unsigned long long*>(S.diag + 8);
-}
-// ... and of the dead shadow rays that were counted instead of queued (prt_shadow_dead): the 8 bytes behind that
-__device__ __forceinline__ unsigned long long* dead_total(const SceneDev& S) {
-  return reinterpret_cast<unsigned long long*>(S.diag + 10);
-}
-// the light-class shadow-queue entries of an item, rebuilt from its light class and its live mask (nee_live) in
-// compact slots from s0 on: ray k of kind 0 goes to point light k, the other kinds have ray 0 alone; vi = the index
-// of the item's visibility word
-__device__ __forceinline__ void queue_live(uint32_t* shq, uint32_t s0, int kind, uint32_t live, uint32_t vi) {
-  const uint32_t l0 = kind == 0 ? 0u : (kind == 2 ? kLightSpot : kLightDir);
-#pragma unroll
-  for (uint32_t k = 0; k < 4; k++)
-    if (live & (1u << k)) shq[s0 + (uint32_t)__popc(live & ((1u << k) - 1u))] = ((l0 + k) << 29) | (4u * vi + k);
-}
-
-// ---- shading of P(iter): NEE set-up -> S(iter), BRDF sample or path-2 start -> P(iter + 1)
-// k_shade2's parameter list as the kernarg segment holds it (explicit arguments in order, each at its natural
-// alignment, as C lays out these members)
-struct Shade2Args {
-  SceneDev S;
-  TraceArgs A;
-  TileMap M;
-  WaveBufs B;
-  uint32_t iter;
-};
-typedef const __attribute__((address_space(4))) Shade2Args* Shade2ArgsPtr;
-// EXT (area light, dielectrics): held to 3 waves/SIMD (168 VGPRs, no spills; unbounded it took 175 and ran 2
-// waves: C5 frame 135.7 -> 132.4 ms).  The plain form runs 4 waves at its natural 125 VGPRs (forcing 5 spilled
-// and was 2 % slower).
-// I0 (plain form): iteration 0 of a pass with pmode kPrimReuse and a light-visibility record (B.lvis), an
-// instantiation of its own so that the shading of every other launch carries nothing for it
-template <bool EXT, bool I0 = false>
-__global__ void __launch_bounds__(kBlock, EXT ? 3 : (I0 ? 4 : 1)) k_shade2(SceneDev S, TraceArgs A, TileMap M, WaveBufs B, uint32_t iter) {
-  static_assert(!(EXT && I0), "the light-visibility record belongs to the plain pipelines");
-  const Shade2ArgsPtr args = (Shade2ArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
-  if (args->iter != iter || args->B.n != B.n) {  // the layout above does not match this compiler's: fail the call
-    if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(S.diag + 1, 1u);
-    return;
-  }
-  __shared__ uint32_t pref[kNSub + 1];
-  __shared__ uint32_t sm[8];
-  const uint32_t* q = (iter & 1) ? B.q1 : B.q0;
-  uint32_t* qn = (iter & 1) ? B.q0 : B.q1;
-  const uint32_t sub = blockIdx.x % kNSub;
-  uint32_t* shcnt = qcounter(B.ctr, iter, 1, sub);
-  uint32_t* ncnt = qcounter(B.ctr, iter + 1, 0, sub);
-  uint32_t* shq = B.shq + (size_t)sub * B.scap;
-  const uint32_t total = load_prefix(B.ctr, iter, 0, pref);
-  const uint32_t fl = A.flags;
-  // software pipeline over the grid-stride chunks: the next chunk's item, info, hit and seed are loaded while this
-  // chunk's item is shaded
-  uint32_t item_n = 0, info_n = 0, seed_n = 0;
-  float4 hh_n = make_float4(kFar, 0.0f, 0.0f, 0.0f);
-  float4 ro_n = make_float4(0.0f, 0.0f, 0.0f, 0.0f), rd_n = ro_n;  // (plain form: the ray too)
-  uint2 lv_n = make_uint2(0u, 0u);                                 // (I0: the entry's light-visibility bytes)
-  auto prefetch = [&](uint32_t cc) {
-    const uint32_t gg = cc * kBlock + threadIdx.x;
-    if (gg < total) {
-      item_n = q[map_slot(pref, gg, B.qcap)];
-      info_n = B.info[item_n];
-      // iteration 0 with primary-hit reuse (plain form only): the hit of the pixel's fixed path-1 primary ray
-      hh_n = (!EXT && iter == 0 && B.pmode != kPrimTrace) ? B.phit[(B.base + item_n) % B.pitems] : B.hit[item_n];
-      if constexpr (I0) lv_n = B.lvis[(B.base + item_n) % B.pitems];
-      seed_n = B.seed[item_n];
-      if (!EXT) { ro_n = B.ro[item_n]; rd_n = B.rd[item_n]; }
-    }
-  };
-  prefetch(blockIdx.x);
-  for (uint32_t c = blockIdx.x; c * kBlock < total; c += gridDim.x) {
-    const float4 ro_c = ro_n, rd_c = rd_n;
-    // The scene and buffer descriptors are read from the kernarg segment inside each chunk (scalar loads, scalar
-    // cache) instead of being held in SGPRs across the loop: their ~90 live words spilled to VGPR lanes (378
-    // v_readlane in the loop) when hoisted.  The empty asm hides the pointer's loop invariance.
-    Shade2ArgsPtr ka = args;
-    asm volatile("" : "+s"(ka));
-    const SceneDev& Sc = *(const SceneDev*)&ka->S;
-    const WaveBufs& Bc = *(const WaveBufs*)&ka->B;
-    const uint32_t g = c * kBlock + threadIdx.x;
-    uint32_t item = 0, info = 0, seed = 0, nr = 0;
-    uint32_t ask = 0, vis0 = 0;  // (I0) the rays to queue, bit 8k = ray k; the visibility word's initial value
-    int kind = 0;
-    float4 hh = make_float4(kFar, 0.0f, 0.0f, 0.0f);
-    const bool active = g < total;
-    if (active) {
-      item = item_n; info = info_n; hh = hh_n;
-      const uint32_t sd = seed_n;
-      const uint2 lv = lv_n;
-      if ((info & 0x1FFu) == 0) Bc.s1[item].w = hh.x;                                        // r1.hit.t
-      if (!EXT && hh.x >= kFar) {  // a miss (:159): the sky radiance (or 0) ends the path (EXT: k_miss2 / k_resmiss2)
-        V3 L = v3(0.0f, 0.0f, 0.0f);
-        if (fl & kSkybox) {
-          const float4 d = EXT ? Bc.rd[item] : rd_c;
-          L = sample_sky_call(Sc.sky, Sc.skyw, Sc.skyh, v3(d.x, d.y, d.z));
-        }
-        Bc.ne[item] = make_float4(L.x, L.y, L.z, 0.0f);
-      }
-      if (hh.x < kFar) {
-        seed = sd;
-        kind = nee_kind(fl, seed);                                                           // :198-214
-        nr = (uint32_t)nee_rays(kind);
-        if constexpr (I0) lvis_split(lv, kind, ask, vis0);
-      }
-    }
-    prefetch(c + gridDim.x);
-    // the block's shadow-ray slots, one atomic (I0: of the rays whose answer is not known yet; the known ones are
-    // counted, not queued).  Every other form appends behind the NEE block, once it knows which rays are live
-    uint32_t s0 = 0, live = 0;  // (!I0) live: the item's light-class shadow rays to queue, bit k = ray k
-    if constexpr (I0)
-      s0 = block_append_skip(shcnt, (uint32_t)__popc(ask), qcounter(B.ctr, B.lslot, 1, sub), lvis_total(S),
-                             nr - (uint32_t)__popc(ask), sm);
-    const uint32_t depth = info & 0xFFu, path = (info >> 8) & 1u;
-    uint32_t status = kStMiss, emissive = 0;
-    bool next = false;
-    bool area_ray = false;
-    if (nr) {
-      const float4 o = EXT ? Bc.ro[item] : ro_c, d = EXT ? Bc.rd[item] : rd_c;
-      const V3 D = v3(d.x, d.y, d.z);
-      const uint32_t pk = __float_as_uint(hh.w);
-      const V3 I = v3(o.x, o.y, o.z) + hh.x * D;                                             // tiny_bvh.h:586
-      const V3 V = -D;
-      const HitAttr ha = hit_attributes(Sc, hit_inst(Sc, pk), hit_prim(Sc, pk), hh.y, hh.z, (fl & kNormalMap) != 0);
-      float4 nk;
-      const V3 brdf = nee_lights(Sc, fl, kind, I, V, ha.N, ha.m, seed, nk, [&](int k, uint32_t light) {
-        if constexpr (I0) {  // compact slots: the asked rays below k come first
-          if (ask & (1u << (8 * k)))
-            shq[s0 + (uint32_t)__popc(ask & ((1u << (8 * k)) - 1u))] = (light << 29) | (4u * item + (uint32_t)k);
-        }
-      });
-      // dead rays (!I0): counted, not queued; their visibility bytes keep the "occluded" 0 stored below
-      if constexpr (!I0) live = Bc.dead ? nee_live(Sc, fl, kind, nk, brdf, Bc.dead > 1u) : (1u << nr) - 1u;
-      // a shadow ray is queued as (light, visibility index) with the item's hit point I stored once: the traversal
-      // kernel rebuilds it (shadow_of, the only reader: an item that queues no light-class ray needs none)
-      if (I0 || live) Bc.hp[item] = make_float4(I.x, I.y, I.z, 0.0f);
-      const V3 e = v3(0.0f, 0.0f, 0.0f) + v3(1.0f, 1.0f, 1.0f) * ha.m.emis;                // :196
-      if (e.x != 0.0f || e.y != 0.0f || e.z != 0.0f) {  // otherwise e is +0 and the resolve rebuilds it
-        Bc.ne[item] = make_float4(e.x, e.y, e.z, 0.0f);
-        emissive = kRiEmissive;
-      }
-      Bc.nb[item] = make_float4(brdf.x, brdf.y, brdf.z, 0.0f);
-      Bc.nk[item] = nk;
-      Bc.vis[item] = I0 ? vis0 : 0u;
-      status = kStNeeEnd;
-      if constexpr (EXT) {
-        // area-light sample (2 draws after the light-class NEE draws) at lit, non-delta, non-dielectric hits
-        reinterpret_cast<uint8_t*>(Bc.vis)[4 * (size_t)Bc.n + item] = 0;
-        if (Sc.area && (fl & kLighted) && ha.kind != kMatDielectric && !delta_lobe(ha.m)) {
-          const float xi1 = random_float(seed), xi2 = random_float(seed);
-          Ray sr;
-          float tmax;
-          V3 fa;
-          if (area_nee(area_light(Sc), I, ha.N, V, ha.m, xi1, xi2, sr, tmax, fa)) {
-            area_ray = true;
-            Bc.ao[item] = make_float4(sr.O.x, sr.O.y, sr.O.z, tmax);
-            Bc.ad[item] = make_float4(sr.D.x, sr.D.y, sr.D.z, 0.0f);
-            Bc.na[item] = make_float4(fa.x, fa.y, fa.z, 0.0f);
-          }
-        }
-      }
-      if ((int)depth != A.bounces - 1) {                                                     // :329
-        if (EXT && ha.kind == kMatDielectric) {                                              // :331-372
-          const Dielectric dl = dielectric_split(I, D, ha.N);
-          const size_t e = (size_t)depth * Bc.n + item;
-          Bc.dro[e] = make_float4(dl.refr.O.x, dl.refr.O.y, dl.refr.O.z, dl.fresnel);
-          Bc.drd[e] = make_float4(dl.refr.D.x, dl.refr.D.y, dl.refr.D.z, 0.0f);
-          Bc.T[e] = make_float4(0.0f, 0.0f, 0.0f, kFar);  // w: the continuation is not BRDF-sampled
-          const uint32_t bit = 1u << depth, keep = ~(0x01010101u << depth);
-          Bc.dst[item] = (Bc.dst[item] & keep) | bit | (dl.has_refr ? 0u : (bit << 24));
-          status = kStNeeCont;
-          Bc.ro[item] = make_float4(dl.refl.O.x, dl.refl.O.y, dl.refl.O.z, 0.0f);
-          Bc.rd[item] = make_float4(dl.refl.D.x, dl.refl.D.y, dl.refl.D.z, 0.0f);
-          Bc.info[item] = (depth + 1u) | (path << 8);
-          next = true;
-        } else {
-          V3 dir, thr;
-          float bp = 2.0f;
-          if (sample_bounce(ha.m, V, ha.N, seed, dir, thr, EXT ? &bp : nullptr)) {           // :376-399
-            status = kStNeeCont;
-            float pdf = 0.0f;
-            if constexpr (EXT)  // MIS density of the sampled direction (kFar: delta lobe or no light sampling)
-              pdf = (bp > 1.0f || !Sc.area || !(fl & kLighted)) ? kFar : brdf_pdf(ha.m, ha.N, V, dir, bp);
-            Bc.T[(size_t)depth * Bc.n + item] = make_float4(thr.x, thr.y, thr.z, pdf);
-            const Ray nr2 = make_ray(I + dir * kEpsilon, dir);                               // :404
-            Bc.ro[item] = make_float4(nr2.O.x, nr2.O.y, nr2.O.z, 0.0f);
-            Bc.rd[item] = make_float4(nr2.D.x, nr2.D.y, nr2.D.z, 0.0f);
-            Bc.info[item] = (depth + 1u) | (path << 8);
-            next = true;
-          }
-        }
-      }
-      Bc.seed[item] = seed;
-    }
-    if constexpr (!I0) {  // only the mask lived across the NEE block: the live rays' slots, the dead ones counted
-      const uint32_t nl = (uint32_t)__popc(live);
-      s0 = block_append_skip(shcnt, nl, qcounter(B.ctr, B.lslot, 1, sub), dead_total(S), nr - nl, sm);
-      queue_live(shq, s0, kind, live, item);
-    }
-    if constexpr (EXT) {  // the area-light shadow rays of the block, one more append
-      const uint32_t a0 = block_append(shcnt, area_ray ? 1u : 0u, sm);
-      if (area_ray) shq[a0] = (kLightArea << 29) | item;
-    }
-    if (active) {
-      if (status != kStNeeCont) {
-        if (EXT && Sc.has_diel) next = diel_next(Bc, item, depth, path);
-        if (!next) next = start_path2(Sc, A, M, Bc, item, path);
-      }
-      Bc.rinfo[item] = depth | (path << 8) | (status << 16) | ((uint32_t)kind << 20) | (next ? kRiQueued : 0u) | emissive |
-                       (EXT ? 0u : kResFresh) | ((I0 && ask) ? kRiLearn : 0u);
-    }
-    const uint32_t slot = block_append(ncnt, next ? 1u : 0u, sm);
-    if (next) qn[sub * Bc.qcap + slot] = item;
-  }
-}
+}  // namespace prt
+#include "prt_shade2.h"  // k_miss2, k_shade2 and their helpers
+namespace prt {
 
 // ---- merged pipeline (B.merge: AA, render mode 0, no extensions).  Shading of P(iter) as k_shade2<false>, each
 // path's records (hit point, NEE record, status, (result, throughput) stack) in its own slot (slot = path, at
@@ -1029,7 +713,7 @@ __host__ inline unsigned producer_blocks(const LaunchCfg& c) {
 
 // one iteration of the merged pipeline: trace P(it) + S(it - 1), resolve P(it - 1), miss + shade P(it)
 hipError_t launch_wave2_iter(const LaunchCfg& c, const SceneDev& S, const TraceArgs& A, const TileMap& M,
-                             const WaveBufs& B, float4* out, WaveTimers* tm, uint32_t it) {
+                             const WaveBufs& B, float4* out, WaveTimers* tm, uint32_t it, bool defer) {
   if (B.n == 0) return hipSuccess;
   const unsigned gprod = producer_blocks(c);
   // k_shade2 over 4x the resident blocks when a call holds >= 2^21 items: the extra blocks queue behind the
@@ -1048,7 +732,15 @@ hipError_t launch_wave2_iter(const LaunchCfg& c, const SceneDev& S, const TraceA
   // primary-hit reuse with a current phit: launch 0 of the plain pipeline has nothing to trace (no shadow rays yet,
   // no path-2 primaries) and is not launched; its two timer events are still recorded, back to back (read_stats
   // reads a pair per iteration; the launch shows as ~0 ms and leaves no PRT_DEBUG_QUEUES timeline record)
-  if (!(it == 0 && B.pmode == kPrimReuse && !B.merge)) launch_trace2(c, S, B, it, iters);
+  // deferred resolve (prt_defer.hip): B's record pointers are plane 0.  This launch's shading gets plane `it`; its
+  // traversal gets vis of plane it - 1, whose bytes the shadow entries of S(it - 1) index (shadow_vis)
+  WaveBufs Bt = B, Bs = B;
+  if (defer) {
+    if (it > 0) Bt.vis = B.vis + (size_t)(it - 1u) * B.n;
+    const size_t o = (size_t)it * B.n;
+    Bs.rinfo += o; Bs.ne += o; Bs.nb += o; Bs.nk += o; Bs.vis += o; Bs.T += o;
+  }
+  if (!(it == 0 && B.pmode == kPrimReuse && !B.merge)) launch_trace2(c, S, Bt, it, iters);
   if (tm) (void)hipEventRecord(tm->ev[4 * it + 1], c.stream);
   const bool ext = (S.area || S.has_diel) && A.mode == 0;
   // the misses' sky radiance: by k_shade2<false> itself, or (extensions: the area light can turn a hit into a miss
@@ -1064,7 +756,9 @@ hipError_t launch_wave2_iter(const LaunchCfg& c, const SceneDev& S, const TraceA
   // iteration 0 of a kPrimReuse pass that holds a light-visibility record uses it (shading) and launch 1 adds to it
   // (resolve): the instantiations of their own
   const bool lrec = B.pmode == kPrimReuse && B.lvis != nullptr && !ext && A.mode == 0;
-  if (it > 0 && B.merge) {
+  if (defer) {  // one resolve per pass, behind the last traversal launch
+    if (it == iters) launch_resolve_pass(c.stream, gdense, S, A, B, iters, out, lrec);
+  } else if (it > 0 && B.merge) {
     if (lrec && it == 1) hipLaunchKernelGGL(k_res2md<true>, dim3(gdense), dim3(kBlock), 0, c.stream, S, A, B, out);
     else hipLaunchKernelGGL(k_res2md<false>, dim3(gdense), dim3(kBlock), 0, c.stream, S, A, B, out);
   } else if (it > 0 && !ext && !sep_miss) {
@@ -1085,6 +779,7 @@ hipError_t launch_wave2_iter(const LaunchCfg& c, const SceneDev& S, const TraceA
     else if (B.merge) hipLaunchKernelGGL(k_shade2m<false>, dim3(gshade), dim3(kBlock), 0, c.stream, S, A, M, B, it);
     else if (A.mode != 0) hipLaunchKernelGGL(k_shade2_debug, dim3(gprod), dim3(kBlock), 0, c.stream, S, A, M, B, it);
     else if (ext) hipLaunchKernelGGL(k_shade2<true>, dim3(gshade), dim3(kBlock), 0, c.stream, S, A, M, B, it);
+    else if (defer) launch_shade2d(c.stream, gshade, S, A, M, Bs, it, i0);
     else if (i0) hipLaunchKernelGGL((k_shade2<false, true>), dim3(gshade), dim3(kBlock), 0, c.stream, S, A, M, B, it);
     else hipLaunchKernelGGL(k_shade2<false>, dim3(gshade), dim3(kBlock), 0, c.stream, S, A, M, B, it);
   }
