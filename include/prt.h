@@ -638,6 +638,13 @@ int prt_get_scene_info(prt_ctx* ctx, prt_scene_info* info);
  * mesh (the copy does not depend on where the mesh sits in the concatenated arrays).  *needed (optional) receives
  * the byte count; nodes == NULL only reports it; bytes < *needed: PRT_ERR_INVALID_ARGUMENT. */
 int prt_read_blas(prt_ctx* ctx, int32_t mesh_index, void* nodes, uint64_t bytes, uint64_t* needed);
+/* (additive in ABI 10) The TriMT leaf records of mesh mesh_index's BLAS (48 bytes each: v0[3], prim, e1[3], 0, e2[3],
+ * 0, in leaf order, record i being what a node's tri_base + offset i names once tri_base is mesh-relative as
+ * prt_read_blas returns it), for tests and tools: waits for the context stream and copies them to host memory.  prim
+ * is the mesh-local primitive index, as the builders write it.  There is one record per reference: the mesh's
+ * triangle count, or more under PRT_BUILDER_HOST_SBVH (a triangle cut by spatial splits sits in several leaves).
+ * *needed, tris == NULL and bytes < *needed as for prt_read_blas. */
+int prt_read_blas_tris(prt_ctx* ctx, int32_t mesh_index, void* tris, uint64_t bytes, uint64_t* needed);
 
 #ifdef __cplusplus
 }

@@ -2171,6 +2171,22 @@ int prt_read_blas(prt_ctx* c, int32_t mi, void* nodes, uint64_t bytes, uint64_t*
   return PRT_OK;
 }
 
+int prt_read_blas_tris(prt_ctx* c, int32_t mi, void* tris, uint64_t bytes, uint64_t* needed) {
+  if (!c) return fail(PRT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  if (c->mesh_host.empty()) return fail(PRT_ERR_NOT_READY, "no meshes: call prt_set_meshes");
+  if (mi < 0 || (size_t)mi >= c->mesh_host.size()) return fail(PRT_ERR_INVALID_ARGUMENT, "mesh index out of range");
+  const MeshHost& mh = c->mesh_info[mi];
+  const uint64_t need = (uint64_t)mh.recs * sizeof(TriMT);
+  if (needed) *needed = need;
+  if (!tris) return PRT_OK;
+  if (bytes < need) return fail(PRT_ERR_INVALID_ARGUMENT, "prt_read_blas_tris: buffer too small");
+  PRT_JOIN(c);
+  HIP_TRY(hipSetDevice(c->device));
+  // (prim is mesh-local in the device array too: nothing to make relative)
+  HIP_TRY(hipMemcpyAsync(tris, c->tris.as<TriMT>() + mh.rec_base, need, hipMemcpyDeviceToHost, c->stream));
+  return wait_stream(c, "prt_read_blas_tris");
+}
+
 int prt_set_bvh_builder(prt_ctx* c, int32_t builder) {
   if (!c || builder < PRT_BUILDER_HOST_SAH || builder > PRT_BUILDER_GPU_PLOC)
     return fail(PRT_ERR_INVALID_ARGUMENT, "bad BLAS builder");

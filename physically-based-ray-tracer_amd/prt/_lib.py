@@ -37,7 +37,7 @@ EXPORTS = [
     "prt_shadow_dead",
     "prt_render_aov_ids", "prt_instance_motion", "prt_reproject_motion",
     "prt_temporal_defaults", "prt_reproject_moments", "prt_denoise_variance_defaults", "prt_denoise_variance",
-    "prt_update_mesh", "prt_read_blas",
+    "prt_update_mesh", "prt_read_blas", "prt_read_blas_tris",
 ]
 SHARD_ID_BYTES = 128
 SHARD_NONE, SHARD_RCCL, SHARD_GROUP = 0, 1, 2  # prt_shard_info.transport
@@ -172,6 +172,7 @@ def load():
         "prt_set_meshes": ([vp, C.POINTER(Mesh), i32], C.c_int),
         "prt_update_mesh": ([vp, i32, C.POINTER(Mesh), u32], C.c_int),
         "prt_read_blas": ([vp, i32, vp, C.c_uint64, C.POINTER(C.c_uint64)], C.c_int),
+        "prt_read_blas_tris": ([vp, i32, vp, C.c_uint64, C.POINTER(C.c_uint64)], C.c_int),
         "prt_set_instances": ([vp, vp, vp, i32], C.c_int),
         "prt_set_lights": ([vp, C.POINTER(Lights)], C.c_int),
         "prt_set_sky": ([vp, vp, i32, i32], C.c_int),

@@ -350,6 +350,15 @@ class Context:
         check(self.L.prt_read_blas(self.h, int(index), buf.ctypes.data, n.value, None))
         return buf.reshape(-1, 80)
 
+    def read_blas_tris(self, index):
+        """prt_read_blas_tris: mesh `index`'s TriMT leaf records as a uint8 array [records, 48] in leaf order, prim
+        mesh-local (one record per reference: more than the triangle count only under BUILDER_HOST_SBVH)."""
+        n = C.c_uint64()
+        check(self.L.prt_read_blas_tris(self.h, int(index), None, 0, C.byref(n)))
+        buf = np.zeros(n.value, np.uint8)
+        check(self.L.prt_read_blas_tris(self.h, int(index), buf.ctypes.data, n.value, None))
+        return buf.reshape(-1, 48)
+
     def set_materials(self, kinds=None):
         """Per-instance material kinds (_lib.MAT_TEXTURED / MAT_DIELECTRIC / MAT_MIRROR), None = all textured."""
         if kinds is None:

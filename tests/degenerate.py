@@ -104,6 +104,22 @@ def big_quad():
     return _heightfield_tris(1, 1, 2.0)
 
 
+def slivers(n=400, seed=2):
+    """n long thin slivers at random angles across a square, every box spanning most of it (the triangles of
+    tests/test_bvh_build.py::test_spatial_splits_duplicate_within_budget): the spatial-split builder cuts them, so its
+    tree holds more records than triangles."""
+    rng = np.random.default_rng(seed)
+    a = rng.uniform(0, np.pi, n)
+    c = rng.uniform(-1, 1, (n, 2))
+    d = np.stack([np.cos(a), np.sin(a)], 1)
+    p0, p1 = c - 6 * d, c + 6 * d
+    w = 0.01 * np.stack([-d[:, 1], d[:, 0]], 1)
+    P = np.zeros((n, 3, 3), F32)
+    P[:, 0, [0, 2]], P[:, 1, [0, 2]], P[:, 2, [0, 2]] = p0, p1, p1 + w
+    P[:, :, 1] = rng.uniform(0, 0.05, n)[:, None]
+    return P
+
+
 def _scene(meshes, instances, name, cam_pos=(0.3, 3.0, -5.0)):
     base = scenes.config_small(4, 4)  # lights, sky, textures
     return dataclasses.replace(base, meshes=meshes, instances=instances, cam_pos=np.array(cam_pos, F32),

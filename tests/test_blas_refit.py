@@ -189,10 +189,10 @@ def test_grid_exponent_is_exact(tmp_path):
 
 
 def test_update_mesh_abi_without_a_device():
-    """Both symbols are exported with the header's signatures, and refuse a NULL context (no device needed)."""
+    """The symbols are exported with the header's signatures, and refuse a NULL context (no device needed)."""
     L = prt.load()
-    assert hasattr(L, "prt_update_mesh") and hasattr(L, "prt_read_blas")
-    assert {"prt_update_mesh", "prt_read_blas"} <= set(_lib.EXPORTS)
+    assert hasattr(L, "prt_update_mesh") and hasattr(L, "prt_read_blas") and hasattr(L, "prt_read_blas_tris")
+    assert {"prt_update_mesh", "prt_read_blas", "prt_read_blas_tris"} <= set(_lib.EXPORTS)
     hdr = open(os.path.join(ROOT, "include", "prt.h")).read()
     assert "#define PRT_IN_DEVICE (1u << 0)" in hdr and _lib.IN_DEVICE == 1
     assert "int prt_update_mesh(prt_ctx* ctx, int32_t mesh_index, const prt_mesh* mesh, uint32_t in_flags);" in hdr
@@ -202,4 +202,7 @@ def test_update_mesh_abi_without_a_device():
     assert L.prt_update_mesh(None, 0, None, _lib.IN_DEVICE) == -1
     n = C.c_uint64(7)
     assert L.prt_read_blas(None, 0, None, 0, C.byref(n)) == -1 and b"NULL" in L.prt_last_error()
+    assert "int prt_read_blas_tris(prt_ctx* ctx, int32_t mesh_index, void* tris, uint64_t bytes, uint64_t* needed);" in hdr
+    assert L.prt_read_blas_tris(None, 0, None, 0, C.byref(n)) == -1 and b"NULL" in L.prt_last_error()
+    assert L.prt_read_blas_tris(None, 0, None, 0, None) == -1 and n.value == 7  # *needed is left alone
     assert L.prt_abi_version() == 10
