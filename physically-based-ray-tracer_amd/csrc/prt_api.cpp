@@ -1,398 +1,35 @@
 // prt_api.cpp -- C-ABI implementation (include/prt.h): device residency of the scene, BLAS build,
-// kernel orchestration.  One host thread per context; all device work on one HIP stream.
+// kernel orchestration.  One host thread per context; all device work on one HIP stream.  The context itself is
+// prt_ctx.h; the image-space passes (denoisers, reprojections) are prt_api_image.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <ctime>
-#include <deque>
 #include <memory>
-#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 
-#include "../../include/prt.h"
 #include "bvh_build.h"
 #include "bvh_gpu.h"
 #include "prt_blas_refit.h"
-#include "prt_blas_refit_gpu.h"
+#include "prt_ctx.h"
 #include "prt_denoise.h"
-#include "prt_launch.h"
 #include "prt_motion.h"
-#include "prt_rccl.h"
-#include "prt_refit.h"
-#include "prt_temporal.h"
-#include "prt_variance.h"
 
 using namespace prt;
+using namespace prt::host;
 
-namespace {
+static thread_local std::string g_err;  // prt_last_error's text: the one copy, behind fail for the other files
 
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
+int prt::host::fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
-
-#define HIP_TRY(expr)                                                                        \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) return fail(PRT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-// device allocation owned by its holder (move-only; freed on destruction)
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
-  DevBuf& operator=(DevBuf&& o) noexcept {
-    if (this != &o) { release(); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; }
-    return *this;
-  }
-  ~DevBuf() { release(); }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-  }
-  // (re)allocate to at least n bytes; contents are not preserved
-  hipError_t ensure(size_t n) {
-    if (n <= bytes && p) return hipSuccess;
-    release();
-    hipError_t e = hipMalloc(&p, n ? n : 16);
-    if (e == hipSuccess) bytes = n ? n : 16;
-    return e;
-  }
-  template <class T>
-  T* as() const { return reinterpret_cast<T*>(p); }
-};
-
-// blocking host -> device copy into a resident buffer.  Callers that may overwrite (or reallocate) a buffer
-// that queued frames still read first drain the context stream (drain()).
-hipError_t upload(DevBuf& b, const void* src, size_t n) {
-  hipError_t e = b.ensure(n);
-  if (e != hipSuccess) return e;
-  if (n) return hipMemcpy(b.p, src, n, hipMemcpyHostToDevice);
-  return hipSuccess;
-}
-
-
-// wavefront state of one item group: the context's own (prt_ctx::ws), or of a concurrent group (prt_ctx::grp)
-// What the hit of a tile-map entry's path-1 primary ray (WaveBufs::phit) is a function of: the camera as the
-// kernels get it (SceneDev cam .. panini: the Panini post-process bends the primary rays), the resolution, the tile
-// map, and the epochs of the geometry and of the instance state (prt_ctx::scene_epoch / inst_epoch).  Zeroed before
-// it is filled (no padding), compared by its bytes.
-struct PrimKey {
-  float cam[12], basis[9], pan_b, pan_d;
-  int32_t panini, W, H, ts, rank, world;
-  uint64_t scene_epoch, inst_epoch;
-};
-struct WaveState {
-  DevBuf wave;
-  WaveBufs wb = {};
-  uint32_t n = 0, levels = 0;
-  bool ext = false, merge = false;
-  bool hasR = false;  // the (result) stack R is allocated: every pass but one with a deferred resolve needs it
-  // deferred resolve (prt_wave2.hip k_resolve_pass): the record planes, one per wavefront iteration (point_planes);
-  // allocated by the first call that defers on this state
-  DevBuf planes;
-  // primary-hit reuse: this state's own copy of the records and the key they were traced under (its stamp)
-  DevBuf phit;
-  PrimKey pkey = {};
-  bool pvalid = false;
-  // light-visibility record (WaveBufs::lvis): valid for the phit it was learned on (pgen counts this state's
-  // dense passes, lgen is the count the record belongs to) and for the lights' positions (lpos: point,
-  // directional, spot; colours, the spot's direction and the flags shape no shadow ray)
-  DevBuf lvis;
-  uint64_t pgen = 0, lgen = 0;
-  float lpos[18] = {};
-  bool lvalid = false;
-};
-// a frame in flight (prt_set_frames_in_flight): the wavefront chain of one call on its own stream.  Slot 0 uses the
-// context's own wavefront state and frame buffer, the others their own; done = the call's last work (the
-// accumulation, and for a sharded frame its gather and untile), which the next call's accumulation waits for
-constexpr int kMaxFlights = 8;
-struct Flight {
-  hipStream_t stream = nullptr;
-  hipEvent_t done = nullptr;
-  WaveState ws;
-  DevBuf frames;
-  bool pending = false;  // done is not yet in the context stream's order
-};
-
-// one pinned staging buffer of ensure_instances' uploads (prt_ctx::stage): reused once its copies have run.  The
-// kStageSlots buffers are allocated when an instance set is first built (pinned allocation in the update path cost
-// 20-190 ms per buffer on the GPU box, profiles/r06_tlas_drift.txt); an update that finds all of them in use waits
-// for the oldest one's copies (the host at most kStageSlots updates ahead of the GPU)
-constexpr size_t kStageSlots = 8;
-// the stream's wait for a worker build: a build takes ~6 ms at 10,000 instances and the jobs of up to kStageSlots
-// queued updates run one after another, so the limit only catches a producer that never comes
-constexpr double kHostWaitLimitS = 120.0;
-struct StageSlot {
-  void* p = nullptr;
-  size_t bytes = 0;
-  hipEvent_t ev = nullptr;
-  bool used = false;
-  bool lost = false;  // an update failed while enqueuing from it: never handed out again (its copies may be pending)
-  uint64_t seq = 0;   // when it was last acquired
-};
-// One copy of the instance state the frames read (prt_ctx::isets): instance records, their refit input, the instance
-// BVH.  An update writes the next copy in the ring while the frames in flight still read theirs; a copy is
-// rewritten only after the context stream has waited for the frames that read it (one event per stream they ran on)
-struct InstSet {
-  DevBuf inst, inst_src, tlas8, tlas_slot;
-  std::vector<std::pair<hipStream_t, hipEvent_t>> uses;  // the last frame that read this copy, per stream
-  size_t nuse = 0;
-};
-// The instance BVH's per-update build (ensure_instances) on the context's worker thread: each update's job builds
-// the tree over that update's instance boxes into the update's pinned staging buffer, then sets the update's flag
-// word; the render stream waits for the flag in a one-lane kernel (launch_wait_host) placed before the tree's
-// upload, so the calling thread never builds nor waits, and the frames already queued run while the worker builds.
-// (A host function, hipLaunchHostFunc, made the next enqueue on the stream block the calling thread until it had
-// run: 5-11 ms per update with frames queued, scripts/inst_update_probe.py.)  Jobs run in submission order and every
-// job sets its flag, also when its build fails; the worker never calls HIP.
-struct TlasJob {
-  const InstSrc* src = nullptr;  // the update's instances (in its pinned staging buffer, uploaded before the tree)
-  int32_t n = 0;
-  char* dst = nullptr;           // pinned: cap Node8 records, then 8 * cap slot words
-  size_t cap = 0;                // nodes the upload moves (a tree over n instances has at most max(n, 1) nodes)
-  int max_depth = 0;             // levels the traversal stacks were sized for (build_tlas8's cap)
-  uint32_t* flag = nullptr;      // coherent pinned word: set to 1 once dst holds the tree
-};
-class TlasWorker {
- public:
-  TlasWorker() : th_([this] { run(); }) {}
-  ~TlasWorker() {  // after the streams are synchronised: the queue is empty (every job's stream wait has ended)
-    {
-      std::lock_guard<std::mutex> g(m_);
-      stop_ = true;
-    }
-    cv_.notify_all();
-    th_.join();
-  }
-  void seed(const BuiltTlas8& t) {  // the tree a failed build falls back to (its instance set's first tree)
-    std::lock_guard<std::mutex> g(m_);
-    good_nodes_ = t.nodes;
-    good_slot_ = t.slot;
-  }
-  void submit(const std::shared_ptr<TlasJob>& j) {
-    {
-      std::lock_guard<std::mutex> g(m_);
-      q_.push_back(j);
-    }
-    cv_.notify_all();
-  }
-  // diagnostics of the finished jobs
-  struct Stats { double ms = 0, cpu_ms = 0; int32_t median = 0, failed = 0; std::string err; };
-  Stats stats() {
-    std::lock_guard<std::mutex> g(m_);
-    return st_;
-  }
-
- private:
-  void run() {
-    for (;;) {
-      std::shared_ptr<TlasJob> j;
-      {
-        std::unique_lock<std::mutex> g(m_);
-        cv_.wait(g, [&] { return stop_ || !q_.empty(); });
-        if (q_.empty()) return;  // stop_ with nothing queued
-        j = q_.front();
-        q_.pop_front();
-      }
-      const auto t0 = std::chrono::steady_clock::now();
-      timespec c0{}, c1{};
-      clock_gettime(CLOCK_THREAD_CPUTIME_ID, &c0);
-      bool median = false, ok = false;
-      std::string err;
-      BuiltTlas8 t;
-      try {  // the instances' world boxes (the same refit_instance as k_refit), the SAH build over them
-        const int32_t m = j->n;
-        std::vector<float> boxes(6 * (size_t)m);
-        for (int32_t i = 0; i < m; i++) {
-          InstDev I;
-          refit_instance(j->src[i], I);
-          std::memcpy(&boxes[6 * (size_t)i], I.bmin, 12);
-          std::memcpy(&boxes[6 * (size_t)i + 3], I.bmax, 12);
-        }
-        t = build_tlas8(boxes.data(), m, j->max_depth);
-        median = t.median;
-        ok = t.nodes.size() <= j->cap && t.depth <= j->max_depth;
-        if (!ok) err = "instance BVH larger than planned";
-      } catch (const std::exception& e) {
-        err = e.what();
-      }
-      std::lock_guard<std::mutex> g(m_);
-      const std::vector<Node8>& nodes = ok ? t.nodes : good_nodes_;  // failed: the last good tree (valid links)
-      const std::vector<uint32_t>& slot = ok ? t.slot : good_slot_;
-      std::memcpy(j->dst, nodes.data(), std::min(nodes.size(), j->cap) * sizeof(Node8));
-      std::memcpy(j->dst + j->cap * sizeof(Node8), slot.data(), std::min(slot.size(), 8 * j->cap) * 4);
-      if (ok) {
-        good_nodes_ = std::move(t.nodes);
-        good_slot_ = std::move(t.slot);
-      } else {
-        st_.failed++;
-        st_.err = err;
-      }
-      clock_gettime(CLOCK_THREAD_CPUTIME_ID, &c1);
-      st_.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-      st_.cpu_ms = (c1.tv_sec - c0.tv_sec) * 1e3 + (c1.tv_nsec - c0.tv_nsec) * 1e-6;
-      st_.median += median ? 1 : 0;
-      __atomic_store_n(j->flag, 1u, __ATOMIC_RELEASE);  // the tree is in dst: the stream's wait ends
-    }
-  }
-  std::mutex m_;
-  std::condition_variable cv_;
-  std::deque<std::shared_ptr<TlasJob>> q_;
-  bool stop_ = false;
-  std::vector<Node8> good_nodes_;
-  std::vector<uint32_t> good_slot_;
-  Stats st_;
-  std::thread th_;  // last: started once the members above exist
-};
-
-struct MeshHost {
-  float bmin[3], bmax[3];
-  int depth;
-  int64_t nodes, leaves;
-  int32_t tris;
-  // prt_update_mesh: the mesh's TriMT records [rec_base, rec_base + recs) (more than tris after spatial splits; its
-  // nodes are [MeshDev::root, + nodes)), its vertex count, and the tree levels of the node pass (empty until the
-  // mesh's first update): level d's nodes are order[level_ends[d - 1] .. level_ends[d]) of the mesh's part of
-  // prt_ctx::rf_order
-  uint32_t rec_base = 0, recs = 0;
-  int32_t verts = 0;
-  std::vector<uint32_t> level_ends;
-};
-
-}  // namespace
-
-struct prt_ctx {
-  int device = 0;
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;
-  // textures
-  std::vector<TexDev> tex_host;
-  DevBuf texels, tex;
-  // meshes
-  std::vector<MeshDev> mesh_host;
-  std::vector<MeshHost> mesh_info;
-  DevBuf nodes8, tris, stri, mesh;
-  int max_depth = 0;
-  int builder = -1;  // BLAS builder (prt_set_bvh_builder): PRT_BUILDER_* (-1: PRT_BUILDER_HOST_SAH)
-  double build_ms = 0;  // wall time of the last prt_set_meshes BLAS builds
-  int built_with = PRT_BUILDER_HOST_SAH;
-  // instances
-  std::vector<float> inst_xf;
-  std::vector<uint32_t> inst_mesh;
-  std::vector<uint32_t> inst_kind;  // prt_set_instance_materials (PRT_MAT_*), textured by default
-  std::vector<InstSrc> inst_stage;  // host side of the refit input (prt_refit.h)
-  // the device instance state, one copy per frame in flight + 1 (InstSet); isets[icur] is what the next frame reads
-  std::vector<InstSet> isets = std::vector<InstSet>(1);
-  size_t icur = 0;
-  // instance BVH (more than kLinearInstances instances, or PRT_TLAS=1), rebuilt for every prt_set_instances as the
-  // reference rebuilds its TLAS every frame (Core/Renderer.cpp:33-41, Core/tiny_bvh.h:1732-1770): the host SAH
-  // build + SAH-optimal collapse (bvh_build.h build_tlas8), on the calling thread when the instance set changes,
-  // on the worker thread (tlas_worker) in stream order for every later update (ensure_instances)
-  bool use_tlas = false;
-  int tlas_depth = 0;    // levels the traversal stacks are sized for (>= the current tree's depth)
-  int32_t tlas_n = -1;   // instance count of the current tree (-1: none)
-  std::unique_ptr<TlasWorker> tlas_worker;
-  int32_t tlas_rebuilds = 0, tlas_async = 0;  // since the instance count last changed (diagnostics)
-  // pinned staging buffers of ensure_instances' uploads (instance sources, a new tree's nodes / slots / refit order;
-  // hipMemcpyAsync from pageable memory may block the host): a buffer is written again only after its copies have
-  // run, so the host never waits on queued frames unless it is kStageSlots updates ahead of the GPU
-  std::vector<StageSlot> stage;
-  uint64_t stage_seq = 0;  // acquisitions so far (StageSlot::seq: the oldest buffer is waited for when all are in use)
-  size_t stage_bytes = 0;  // the size the pool was last allocated for
-  uint32_t* stage_flag = nullptr;      // one coherent pinned word per staging buffer (64-B stride): TlasJob::flag
-  uint32_t* stage_flag_dev = nullptr;  // its device address
-  // prt_update_mesh (prt_blas_refit.h), allocated at a context's first update for the scene as it stands and kept:
-  // six floats per node (the uninflated boxes), the nodes of every refitted mesh ordered by tree level, the 28-byte
-  // result (root box, bad-index flag) and its pinned host copy; for host arrays, the six arrays back to back in one
-  // pinned buffer (written again once rf_ev says the previous update's copy has run) and their device copy
-  DevBuf rf_box, rf_order, rf_res, rf_in;
-  RefitResult* rf_res_host = nullptr;
-  void* rf_pin = nullptr;
-  size_t rf_pin_bytes = 0;
-  hipEvent_t rf_ev = nullptr;
-  bool rf_pin_used = false;
-  DevBuf spill;  // traversal stack levels beyond the LDS ones (BVHs deeper than 17 levels)
-  DevBuf diag;   // SceneDev::diag device counters ([0] traversal stack overflows, cumulative per context)
-  // area light (prt_set_area_lights): p0, eu, ev, n, Le, area
-  float al[16] = {};
-  int32_t area = 0, area_two_sided = 0;
-  bool inst_dirty = true;  // the device instance records (k_refit) are out of date
-  bool tlas_dirty = true;  // transforms or meshes changed since the instance BVH was last built / refitted
-  // sky, lights, camera
-  DevBuf sky;
-  int32_t skyw = 0, skyh = 0;
-  DevBuf srgb;  // 256-entry sRGB -> linear table of the albedo decode
-  prt_lights lights{};
-  bool have_lights = false;
-  prt_camera cam{};
-  bool have_camera = false;
-  prt_postfx pfx{};  // post-processing off until prt_set_postfx
-  DevBuf accprev;    // accumulator before the last frame of a call (screen-pass aberration)
-  // accumulation state (Core/Renderer.h:61-63) and scratch
-  DevBuf acc, nsamp, dist;
-  int32_t accW = 0, accH = 0;
-  DevBuf frames, avg, rgb8, counters, hits, tl;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  // wavefront state of the merged pipeline (frame-in-flight slot 0 and calls in the context stream's order)
-  WaveState ws;
-  WaveTimers wt = {};
-  // the last enqueued render, for its stats (read_stats)
-  uint32_t last_iters = 0;
-  bool last_defer = false;  // the last call's passes ran the deferred resolve (prt_stats::pipeline)
-  bool last_timers = false;
-  uint64_t last_paths = 0;
-  uint64_t carry_segments = 0, carry_shadow = 0;  // ray counts of a call's earlier frame passes
-  // primary-hit reuse (PrimKey): scene_epoch counts the calls that change geometry or BLASes (prt_set_meshes,
-  // prt_set_bvh_builder), inst_epoch those that change the instance records, the instance BVH or the hit word's
-  // encoding (prt_set_instances); prim_traced / prim_reused: path-1 primary rays handed to a dense pass / taken
-  // from phit by the calls so far (host bookkeeping, prt_primary_rays)
-  uint64_t scene_epoch = 0, inst_epoch = 0;
-  uint64_t prim_traced = 0, prim_reused = 0;
-  // sharding (prt_shard_init_rccl / prt_shard_attach_rccl / prt_create_group)
-  int32_t sh_kind = 0;  // 0 none, 1 RCCL, 2 local group (this context is member 0)
-  int32_t sh_rank = 0, sh_world = 1, sh_tile = 32;
-  ncclComm_t comm = nullptr;
-  bool own_comm = false;
-  std::vector<prt_ctx*> members;  // local group: members 1..world-1, owned by member 0
-  DevBuf shtiles, gathered;       // this rank's tile buffer; rank 0: [world][tile buffer] gathered
-  hipEvent_t sh_ev = nullptr;     // member: tiles handed to member 0; member 0: untile done
-  bool layout_checked = false;    // check_layout_once done
-  // frames in flight (prt_set_frames_in_flight): 1 = every call complete in the context stream's order
-  int32_t inflight = 1;
-  Flight fl[kMaxFlights];
-  int32_t next_fl = 0, last_fl = -1;  // the slot of the next call / of the last call still ordering accumulation
-  hipEvent_t fl_fork = nullptr;
-  // first-hit AOVs and the denoiser (prt_render_aov / prt_denoise): primary hits, staging of host inputs / outputs,
-  // the packed unit normal + depth, and the two buffers the filter iterations alternate between
-  DevBuf aov_hits, aov_alb, aov_nd;
-  DevBuf dn_in[3], dn_geo, dn_pp[2], dn_out, dn_rgb8;
-  hipEvent_t dn_ev[2 + PRT_DENOISE_TIMINGS] = {};  // PRT_OUT_TIMED: [0..1] the AOV pass, [2..] prep + iterations
-  int32_t dn_timed_aov = 0, dn_timed_passes = 0;   // what the last timed calls recorded
-  // temporal reprojection (prt_reproject): staging of host images (colour, normal_depth, history, its normal_depth)
-  DevBuf rp_in[4], rp_out, rp_rgb8;
-  // instance ids and motion (prt_render_aov_ids / prt_reproject_motion): the id output's staging, the staging of host
-  // id images (this view's, the previous view's) and the motion matrices on the device
-  DevBuf aov_ids, rp_ids[2], rp_motion;
-  // moments and variance (prt_reproject_moments / prt_denoise_variance): the staging of host moments images (the
-  // previous one, the output; the filter's input) and of the filter's variance output
-  DevBuf rp_mom[2], dn_mom, dn_var;
-};
 
 namespace {
 
@@ -404,9 +41,11 @@ constexpr int kMaxBvhDepth = 64;
 int stack_depth(const prt_ctx* c) { return c->max_depth + (c->use_tlas ? c->tlas_depth : 0); }
 bool depth_ok(const prt_ctx* c) { return stack_depth(c) <= kMaxBvhDepth; }
 
+}  // namespace
+
 // frames in flight: the context stream waits for every call still in flight.  Every entry point but an in-flight
 // prt_render starts with it, so its work (and the host waits of drain()) comes after those frames
-int join_flights(prt_ctx* c) {
+int prt::host::join_flights(prt_ctx* c) {
   if (c->last_fl < 0) return PRT_OK;
   HIP_TRY(hipSetDevice(c->device));
   for (Flight& f : c->fl)
@@ -417,6 +56,8 @@ int join_flights(prt_ctx* c) {
   c->last_fl = -1;  // the next call's accumulation is ordered through the context stream again
   return PRT_OK;
 }
+
+namespace {
 
 // RCCL calls and waits that involve the peers are bounded (failure detection): a rank whose peers never
 // arrive -- at communicator set-up or in a frame's ncclGather -- fails after PRT_RCCL_TIMEOUT_S seconds (default
@@ -494,9 +135,11 @@ int occ_at(int d) {  // the occupancy a stack of d levels allows (7 waves: re-me
 }
 int occ_for(const prt_ctx* c) { return occ_at(stack_depth(c)); }
 
+}  // namespace
+
 // a pinned staging buffer of at least `bytes` (prt_ctx::stage): a free one (its copies have run), a new one while
 // the pool holds fewer than kStageSlots, else the oldest once its copies have run (the only host wait)
-int stage_acquire(prt_ctx* c, size_t bytes, StageSlot*& out) {
+int prt::host::stage_acquire(prt_ctx* c, size_t bytes, StageSlot*& out) {
   StageSlot* pick = nullptr;
   for (StageSlot& t : c->stage) {
     if (t.lost) continue;
@@ -536,11 +179,13 @@ int stage_acquire(prt_ctx* c, size_t bytes, StageSlot*& out) {
   return PRT_OK;
 }
 // the copies out of the buffer are enqueued: it is free again once the stream has run them
-int stage_release(prt_ctx*, StageSlot& st, hipStream_t s) {
+int prt::host::stage_release(prt_ctx*, StageSlot& st, hipStream_t s) {
   HIP_TRY(hipEventRecord(st.ev, s));
   st.used = true;
   return PRT_OK;
 }
+
+namespace {
 
 // Instance records on the device (prt_refit.h: MESA inverse, normal matrix, inflated world box): one async copy of
 // the transforms + k_refit on the render stream, so frames already queued keep reading the previous instances.
@@ -1619,13 +1264,6 @@ int shard_setup(prt_ctx* c, int32_t tile) {
   return PRT_OK;
 }
 
-// every entry point but an in-flight prt_render first joins the frames in flight (join_flights)
-#define PRT_JOIN(ctx)                       \
-  do {                                      \
-    const int rcj_ = join_flights(ctx);     \
-    if (rcj_) return rcj_;                  \
-  } while (0)
-
 // a setter of a local group applies to every member (member 0 = the group context itself)
 #define PRT_FOR_MEMBERS(call)                 \
   do {                                         \
@@ -2617,17 +2255,17 @@ int prt_trace_primary(prt_ctx* c, int32_t W, int32_t H, prt_hit* hits, uint32_t 
   rc = ensure_spill(c, S, (size_t)M.items + 256);
   if (rc) return rc;
   HitOut* out = reinterpret_cast<HitOut*>(hits);
-  const bool dev_out = (out_flags & PRT_OUT_DEVICE) != 0;
-  if (!dev_out) { HIP_TRY(c->hits.ensure(n * sizeof(HitOut))); out = c->hits.as<HitOut>(); }
+  Staging io(c, out_flags);
+  PRT_TRY(io.out(c->hits, out, n * sizeof(HitOut)));
   HIP_TRY(c->counters.ensure(sizeof(Counters)));
   HIP_TRY(hipMemsetAsync(c->counters.p, 0, sizeof(Counters), c->stream));
   LaunchCfg L{c->stream, occ_for(c)};
   HIP_TRY(hipEventRecord(c->ev[0], c->stream));
   HIP_TRY(launch_primary_hits(L, S, M, out, c->counters.as<Counters>()));
   HIP_TRY(hipEventRecord(c->ev[2], c->stream));
-  if (!dev_out) HIP_TRY(hipMemcpyAsync(hits, out, n * sizeof(HitOut), hipMemcpyDeviceToHost, c->stream));
-  if (stats || !dev_out) HIP_TRY(hipStreamSynchronize(c->stream));
+  PRT_TRY(io.finish());
   if (stats) {
+    if (io.dev) HIP_TRY(hipStreamSynchronize(c->stream));
     Counters h{};
     HIP_TRY(hipMemcpy(&h, c->counters.p, sizeof(h), hipMemcpyDeviceToHost));
     float ms = 0;
@@ -2684,15 +2322,6 @@ int prt_occluded(prt_ctx* c, int32_t n, const float* O, const float* D, const fl
 
 // ---- first-hit AOVs and the a-trous denoiser (prt_denoise.hip)
 namespace {
-int dn_event(prt_ctx* c, int k) {  // record timing event k on the context stream
-  if (!c->dn_ev[k]) HIP_TRY(hipEventCreate(&c->dn_ev[k]));
-  HIP_TRY(hipEventRecord(c->dn_ev[k], c->stream));
-  return PRT_OK;
-}
-bool sigma_ok(float v, bool zero_ok) { return std::isfinite(v) && (zero_ok ? v >= 0.0f : v > 0.0f); }
-}  // namespace
-
-namespace {
 // prt_render_aov / prt_render_aov_ids: one primary-hit pass, then k_aov and / or k_aov_ids over its hits
 int render_aov(prt_ctx* c, int32_t W, int32_t H, uint32_t flags, float* albedo, float* normal_depth,
                uint32_t* instance, uint32_t out_flags) {
@@ -2709,17 +2338,16 @@ int render_aov(prt_ctx* c, int32_t W, int32_t H, uint32_t flags, float* albedo, 
   const size_t n = (size_t)W * H;
   rc = ensure_spill(c, S, (size_t)M.items + 256);
   if (rc) return rc;
-  const bool dev_out = (out_flags & PRT_OUT_DEVICE) != 0, timed = (out_flags & PRT_OUT_TIMED) != 0;
+  const bool timed = (out_flags & PRT_OUT_TIMED) != 0;
   HIP_TRY(c->aov_hits.ensure(n * sizeof(HitOut)));
   HIP_TRY(c->counters.ensure(sizeof(Counters)));  // the launch's own ray count: not the running totals
   float4* a = reinterpret_cast<float4*>(albedo);
   float4* g = reinterpret_cast<float4*>(normal_depth);
   uint32_t* ids = instance;
-  if (!dev_out) {
-    if (albedo) { HIP_TRY(c->aov_alb.ensure(n * sizeof(float4))); a = c->aov_alb.as<float4>(); }
-    if (normal_depth) { HIP_TRY(c->aov_nd.ensure(n * sizeof(float4))); g = c->aov_nd.as<float4>(); }
-    if (instance) { HIP_TRY(c->aov_ids.ensure(n * 4)); ids = c->aov_ids.as<uint32_t>(); }
-  }
+  Staging io(c, out_flags);
+  PRT_TRY(io.out(c->aov_alb, a, n * sizeof(float4)));
+  PRT_TRY(io.out(c->aov_nd, g, n * sizeof(float4)));
+  PRT_TRY(io.out(c->aov_ids, ids, n * 4));
   LaunchCfg L{c->stream, occ_for(c)};
   if (timed && (rc = dn_event(c, 0))) return rc;
   HIP_TRY(launch_primary_hits(L, S, M, c->aov_hits.as<HitOut>(), c->counters.as<Counters>()));
@@ -2730,13 +2358,7 @@ int render_aov(prt_ctx* c, int32_t W, int32_t H, uint32_t flags, float* albedo, 
     if ((rc = dn_event(c, 1))) return rc;
     c->dn_timed_aov = 1;
   }
-  if (!dev_out) {
-    if (albedo) HIP_TRY(hipMemcpyAsync(albedo, a, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    if (normal_depth) HIP_TRY(hipMemcpyAsync(normal_depth, g, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    if (instance) HIP_TRY(hipMemcpyAsync(instance, ids, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-  }
-  return PRT_OK;
+  return io.finish();
 }
 }  // namespace
 
@@ -2747,489 +2369,6 @@ int prt_render_aov(prt_ctx* c, int32_t W, int32_t H, uint32_t flags, float* albe
 int prt_render_aov_ids(prt_ctx* c, int32_t W, int32_t H, uint32_t flags, float* albedo, float* normal_depth,
                        uint32_t* instance, uint32_t out_flags) {
   return render_aov(c, W, H, flags, albedo, normal_depth, instance, out_flags);
-}
-
-int prt_denoise_defaults(prt_denoise_params* out) {
-  if (!out) return fail(PRT_ERR_INVALID_ARGUMENT, "out is NULL");
-  out->iterations = 5;
-  out->normal_power = 3;
-  out->sigma_color = 4.0f;
-  out->sigma_depth = 0.1f;
-  out->sigma_albedo = 0.25f;
-  return PRT_OK;
-}
-
-int prt_denoise(prt_ctx* c, const prt_denoise_params* p, int32_t W, int32_t H, const float* color, const float* albedo,
-                const float* normal_depth, float* out_rgba, uint32_t* out_rgb8, uint32_t out_flags) {
-  if (!c || !p || !color || !normal_depth || (!out_rgba && !out_rgb8) || W <= 0 || H <= 0 || W > 16384 || H > 16384)
-    return fail(PRT_ERR_INVALID_ARGUMENT, "bad denoise arguments");
-  if (p->iterations < 1 || p->iterations > 8 || p->normal_power < 0 || p->normal_power > 7 ||
-      !sigma_ok(p->sigma_color, false) || !sigma_ok(p->sigma_depth, false) || !sigma_ok(p->sigma_albedo, true))
-    return fail(PRT_ERR_INVALID_ARGUMENT, "denoise parameters out of range");
-  const bool use_albedo = p->sigma_albedo > 0.0f;
-  if (use_albedo && !albedo) return fail(PRT_ERR_INVALID_ARGUMENT, "albedo is NULL with sigma_albedo > 0");
-  PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t n = (size_t)W * H, bytes = n * sizeof(float4);
-  const bool dev = (out_flags & PRT_OUT_DEVICE) != 0, timed = (out_flags & PRT_OUT_TIMED) != 0;
-  const float4* src[3] = {reinterpret_cast<const float4*>(color), reinterpret_cast<const float4*>(normal_depth),
-                          use_albedo ? reinterpret_cast<const float4*>(albedo) : nullptr};
-  float4* dst = reinterpret_cast<float4*>(out_rgba);
-  uint32_t* dst8 = out_rgb8;
-  if (!dev) {  // host images: staged in context buffers
-    for (int k = 0; k < 3; k++) {
-      if (!src[k]) continue;
-      HIP_TRY(c->dn_in[k].ensure(bytes));
-      HIP_TRY(hipMemcpyAsync(c->dn_in[k].p, src[k], bytes, hipMemcpyHostToDevice, c->stream));
-      src[k] = c->dn_in[k].as<float4>();
-    }
-    if (out_rgba) { HIP_TRY(c->dn_out.ensure(bytes)); dst = c->dn_out.as<float4>(); }
-    if (out_rgb8) { HIP_TRY(c->dn_rgb8.ensure(n * 4)); dst8 = c->dn_rgb8.as<uint32_t>(); }
-  }
-  HIP_TRY(c->dn_geo.ensure(bytes));
-  if (p->iterations > 1 || dst == src[0]) {
-    HIP_TRY(c->dn_pp[0].ensure(bytes));
-    if (p->iterations > 2) HIP_TRY(c->dn_pp[1].ensure(bytes));
-  }
-  int rc = PRT_OK;
-  if (timed && (rc = dn_event(c, 2))) return rc;
-  HIP_TRY(launch_denoise_prep(c->stream, W, H, src[1], c->dn_geo.as<float4>()));
-  if (timed && (rc = dn_event(c, 3))) return rc;
-  const float4* in = src[0];
-  if (p->iterations == 1 && dst == in) {  // a single pass in place: filter a copy
-    HIP_TRY(hipMemcpyAsync(c->dn_pp[0].p, in, bytes, hipMemcpyDeviceToDevice, c->stream));
-    in = c->dn_pp[0].as<float4>();
-  }
-  for (int32_t i = 0; i < p->iterations; i++) {
-    const bool last = i == p->iterations - 1;
-    const float sc = p->sigma_color * std::ldexp(1.0f, -i);
-    DenoisePass P{};
-    P.W = W;
-    P.H = H;
-    P.step = 1 << i;
-    P.normal_power = p->normal_power;
-    P.sc2 = sc * sc;
-    P.sigma_depth = p->sigma_depth;
-    P.sa2 = p->sigma_albedo * p->sigma_albedo;
-    P.color = in;
-    P.geo = c->dn_geo.as<float4>();
-    P.albedo = src[2];
-    P.out = last ? dst : c->dn_pp[i & 1].as<float4>();
-    P.rgb8 = last ? dst8 : nullptr;
-    HIP_TRY(launch_denoise_pass(c->stream, P));
-    if (timed && (rc = dn_event(c, 4 + i))) return rc;
-    in = P.out;
-  }
-  if (timed) c->dn_timed_passes = p->iterations;
-  if (!dev) {
-    if (out_rgba) HIP_TRY(hipMemcpyAsync(out_rgba, dst, bytes, hipMemcpyDeviceToHost, c->stream));
-    if (out_rgb8) HIP_TRY(hipMemcpyAsync(out_rgb8, dst8, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-  }
-  return PRT_OK;
-}
-
-int prt_denoise_timings(prt_ctx* c, float* ms, int32_t count) {
-  if (!c || !ms || count < 1 || count > PRT_DENOISE_TIMINGS) return fail(PRT_ERR_INVALID_ARGUMENT, "bad timing arguments");
-  PRT_JOIN(c);
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  float t[PRT_DENOISE_TIMINGS] = {};
-  if (c->dn_timed_aov) HIP_TRY(hipEventElapsedTime(&t[0], c->dn_ev[0], c->dn_ev[1]));
-  for (int32_t k = 0; c->dn_timed_passes > 0 && k < 1 + c->dn_timed_passes; k++)
-    HIP_TRY(hipEventElapsedTime(&t[1 + k], c->dn_ev[2 + k], c->dn_ev[3 + k]));
-  for (int32_t k = 0; k < count; k++) ms[k] = t[k];
-  return PRT_OK;
-}
-
-// ---- temporal reprojection (prt_temporal.hip)
-int prt_reproject_defaults(prt_reproject_params* out) {
-  if (!out) return fail(PRT_ERR_INVALID_ARGUMENT, "out is NULL");
-  out->depth_tol = 0.05f;
-  out->normal_min = 0.9f;
-  out->max_history = 16.0f;
-  return PRT_OK;
-}
-
-int prt_reproject(prt_ctx* c, const prt_reproject_params* p, int32_t W, int32_t H, const prt_camera* cam,
-                  const float* color, const float* normal_depth, const prt_camera* prev_cam, const float* history,
-                  const float* history_nd, float* out_rgba, uint32_t* out_rgb8, uint32_t out_flags) {
-  if (!c || !p || !cam || !color || !normal_depth || (!out_rgba && !out_rgb8) || W <= 0 || H <= 0 || W > 16384 ||
-      H > 16384)
-    return fail(PRT_ERR_INVALID_ARGUMENT, "bad reproject arguments");
-  if (!sigma_ok(p->depth_tol, true) || !(p->normal_min >= -1.0f && p->normal_min <= 1.0f) ||
-      !std::isfinite(p->max_history) || p->max_history < 1.0f)
-    return fail(PRT_ERR_INVALID_ARGUMENT, "reproject parameters out of range");
-  const int given = (prev_cam ? 1 : 0) + (history ? 1 : 0) + (history_nd ? 1 : 0);
-  if (given != 0 && given != 3)
-    return fail(PRT_ERR_INVALID_ARGUMENT, "prev_camera, history_rgba and history_normal_depth go together");
-  if (out_rgba && given && (out_rgba == history || out_rgba == history_nd))
-    return fail(PRT_ERR_INVALID_ARGUMENT, "out_rgba must not be a history buffer");
-  PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t n = (size_t)W * H, bytes = n * sizeof(float4);
-  const bool dev = (out_flags & PRT_OUT_DEVICE) != 0;
-  const float4* src[4] = {reinterpret_cast<const float4*>(color), reinterpret_cast<const float4*>(normal_depth),
-                          reinterpret_cast<const float4*>(history), reinterpret_cast<const float4*>(history_nd)};
-  float4* dst = reinterpret_cast<float4*>(out_rgba);
-  uint32_t* dst8 = out_rgb8;
-  if (!dev) {  // host images: staged in context buffers
-    for (int k = 0; k < 4; k++) {
-      if (!src[k]) continue;
-      HIP_TRY(c->rp_in[k].ensure(bytes));
-      HIP_TRY(hipMemcpyAsync(c->rp_in[k].p, src[k], bytes, hipMemcpyHostToDevice, c->stream));
-      src[k] = c->rp_in[k].as<float4>();
-    }
-    if (out_rgba) { HIP_TRY(c->rp_out.ensure(bytes)); dst = c->rp_out.as<float4>(); }
-    if (out_rgb8) { HIP_TRY(c->rp_rgb8.ensure(n * 4)); dst8 = c->rp_rgb8.as<uint32_t>(); }
-  }
-  ReprojectPass P{};
-  P.W = W;
-  P.H = H;
-  P.depth_tol = p->depth_tol;
-  P.normal_min = p->normal_min;
-  P.max_history = p->max_history;
-  make_reproject_pass(P, *cam, prev_cam);
-  P.color = src[0];
-  P.nd = src[1];
-  P.hist = src[2];
-  P.hist_nd = src[3];
-  P.out = dst;
-  P.rgb8 = dst8;
-  HIP_TRY(launch_reproject(c->stream, P));
-  if (!dev) {
-    if (out_rgba) HIP_TRY(hipMemcpyAsync(out_rgba, dst, bytes, hipMemcpyDeviceToHost, c->stream));
-    if (out_rgb8) HIP_TRY(hipMemcpyAsync(out_rgb8, dst8, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-  }
-  return PRT_OK;
-}
-
-// ---- moving instances in the temporal reprojection (prt_motion.hip)
-int prt_instance_motion(const float* transforms, const float* prev_transforms, int32_t count, float* motion) {
-  if (count < 0 || (count > 0 && (!transforms || !prev_transforms || !motion)))
-    return fail(PRT_ERR_INVALID_ARGUMENT, "bad instance motion arguments");
-  static const float kIdentity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-  for (int32_t k = 0; k < count; k++) {
-    const float* T = transforms + 16 * (size_t)k;
-    const float* Q = prev_transforms + 16 * (size_t)k;
-    float* A = motion + 12 * (size_t)k;
-    std::memcpy(A, kIdentity, sizeof(kIdentity));
-    if (std::memcmp(T, Q, 16 * sizeof(float)) == 0) continue;  // at rest: the exact identity
-    double m[3][3], t[3];
-    bool finite = true;
-    for (int r = 0; r < 3; r++) {
-      for (int j = 0; j < 3; j++) m[r][j] = T[4 * r + j];
-      t[r] = T[4 * r + 3];
-      for (int j = 0; j < 4; j++) finite = finite && std::isfinite(T[4 * r + j]);
-    }
-    const double c00 = m[1][1] * m[2][2] - m[1][2] * m[2][1], c01 = m[1][2] * m[2][0] - m[1][0] * m[2][2],
-                 c02 = m[1][0] * m[2][1] - m[1][1] * m[2][0];
-    const double det = m[0][0] * c00 + m[0][1] * c01 + m[0][2] * c02;
-    if (!finite || det == 0.0 || !std::isfinite(1.0 / det)) continue;  // no visible pixel: identity
-    const double id = 1.0 / det;
-    const double inv[3][3] = {
-        {c00 * id, (m[0][2] * m[2][1] - m[0][1] * m[2][2]) * id, (m[0][1] * m[1][2] - m[0][2] * m[1][1]) * id},
-        {c01 * id, (m[0][0] * m[2][2] - m[0][2] * m[2][0]) * id, (m[0][2] * m[1][0] - m[0][0] * m[1][2]) * id},
-        {c02 * id, (m[0][1] * m[2][0] - m[0][0] * m[2][1]) * id, (m[0][0] * m[1][1] - m[0][1] * m[1][0]) * id}};
-    for (int r = 0; r < 3; r++) {  // A = [Mp * inv, tp - Mp * inv * t]
-      double row[3], tr = Q[4 * r + 3];
-      for (int j = 0; j < 3; j++) {
-        row[j] = ((double)Q[4 * r] * inv[0][j] + (double)Q[4 * r + 1] * inv[1][j]) + (double)Q[4 * r + 2] * inv[2][j];
-        tr -= row[j] * t[j];
-      }
-      for (int j = 0; j < 3; j++) A[4 * r + j] = (float)row[j];
-      A[4 * r + 3] = (float)tr;
-    }
-  }
-  return PRT_OK;
-}
-
-int prt_reproject_motion(prt_ctx* c, const prt_reproject_params* p, int32_t W, int32_t H, const prt_camera* cam,
-                         const float* color, const float* normal_depth, const uint32_t* instance,
-                         const prt_camera* prev_cam, const float* history, const float* history_nd,
-                         const uint32_t* history_inst, const float* motion, int32_t count, float* out_rgba,
-                         uint32_t* out_rgb8, uint32_t out_flags) {
-  if (!c || !p || !cam || !color || !normal_depth || (!out_rgba && !out_rgb8) || W <= 0 || H <= 0 || W > 16384 ||
-      H > 16384)
-    return fail(PRT_ERR_INVALID_ARGUMENT, "bad reproject arguments");
-  if (!sigma_ok(p->depth_tol, true) || !(p->normal_min >= -1.0f && p->normal_min <= 1.0f) ||
-      !std::isfinite(p->max_history) || p->max_history < 1.0f)
-    return fail(PRT_ERR_INVALID_ARGUMENT, "reproject parameters out of range");
-  const int given = (prev_cam ? 1 : 0) + (history ? 1 : 0) + (history_nd ? 1 : 0) + (motion ? 1 : 0) + (count ? 1 : 0);
-  if (count < 0 || (given != 0 && given != 5) || (given == 0 && history_inst))
-    return fail(PRT_ERR_INVALID_ARGUMENT,
-                "prev_camera, history_rgba, history_normal_depth, motion and count > 0 go together");
-  if (given && !instance) return fail(PRT_ERR_INVALID_ARGUMENT, "instance is NULL with a history");
-  if (out_rgba && given && (out_rgba == history || out_rgba == history_nd))
-    return fail(PRT_ERR_INVALID_ARGUMENT, "out_rgba must not be a history buffer");
-  if (out_rgb8 && history_inst && out_rgb8 == history_inst)
-    return fail(PRT_ERR_INVALID_ARGUMENT, "out_rgb8 must not be history_instance");
-  PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t n = (size_t)W * H, bytes = n * sizeof(float4);
-  const bool dev = (out_flags & PRT_OUT_DEVICE) != 0;
-  const float4* src[4] = {reinterpret_cast<const float4*>(color), reinterpret_cast<const float4*>(normal_depth),
-                          reinterpret_cast<const float4*>(history), reinterpret_cast<const float4*>(history_nd)};
-  const uint32_t* ids[2] = {given ? instance : nullptr, history_inst};
-  float4* dst = reinterpret_cast<float4*>(out_rgba);
-  uint32_t* dst8 = out_rgb8;
-  if (!dev) {  // host images: staged in context buffers
-    for (int k = 0; k < 4; k++) {
-      if (!src[k]) continue;
-      HIP_TRY(c->rp_in[k].ensure(bytes));
-      HIP_TRY(hipMemcpyAsync(c->rp_in[k].p, src[k], bytes, hipMemcpyHostToDevice, c->stream));
-      src[k] = c->rp_in[k].as<float4>();
-    }
-    for (int k = 0; k < 2; k++) {
-      if (!ids[k]) continue;
-      HIP_TRY(c->rp_ids[k].ensure(n * 4));
-      HIP_TRY(hipMemcpyAsync(c->rp_ids[k].p, ids[k], n * 4, hipMemcpyHostToDevice, c->stream));
-      ids[k] = c->rp_ids[k].as<uint32_t>();
-    }
-    if (out_rgba) { HIP_TRY(c->rp_out.ensure(bytes)); dst = c->rp_out.as<float4>(); }
-    if (out_rgb8) { HIP_TRY(c->rp_rgb8.ensure(n * 4)); dst8 = c->rp_rgb8.as<uint32_t>(); }
-  }
-  if (given) {  // the matrices: copied into a pinned staging buffer now, uploaded in stream order (no host wait)
-    const size_t mb = 12 * sizeof(float) * (size_t)count;
-    HIP_TRY(c->rp_motion.ensure(mb));
-    StageSlot* st = nullptr;
-    const int rc = stage_acquire(c, mb, st);
-    if (rc) return rc;
-    std::memcpy(st->p, motion, mb);
-    HIP_TRY(hipMemcpyAsync(c->rp_motion.p, st->p, mb, hipMemcpyHostToDevice, c->stream));
-    const int rr = stage_release(c, *st, c->stream);
-    if (rr) return rr;
-  }
-  MotionPass P{};
-  P.R.W = W;
-  P.R.H = H;
-  P.R.depth_tol = p->depth_tol;
-  P.R.normal_min = p->normal_min;
-  P.R.max_history = p->max_history;
-  make_reproject_pass(P.R, *cam, prev_cam);
-  P.R.color = src[0];
-  P.R.nd = src[1];
-  P.R.hist = src[2];
-  P.R.hist_nd = src[3];
-  P.R.out = dst;
-  P.R.rgb8 = dst8;
-  P.inst = ids[0];
-  P.hist_inst = ids[1];
-  P.motion = given ? c->rp_motion.as<float4>() : nullptr;
-  P.count = count;
-  HIP_TRY(launch_reproject_motion(c->stream, P));
-  if (!dev) {
-    if (out_rgba) HIP_TRY(hipMemcpyAsync(out_rgba, dst, bytes, hipMemcpyDeviceToHost, c->stream));
-    if (out_rgb8) HIP_TRY(hipMemcpyAsync(out_rgb8, dst8, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-  }
-  return PRT_OK;
-}
-
-// ---- luminance moments and the variance-guided filter (prt_variance.hip)
-int prt_temporal_defaults(prt_temporal_params* out) {
-  if (!out) return fail(PRT_ERR_INVALID_ARGUMENT, "out is NULL");
-  out->depth_tol = 0.05f;
-  out->normal_min = 0.9f;
-  out->max_history = 16.0f;
-  out->clamp_k = 0.0f;
-  out->min_temporal = 4.0f;
-  return PRT_OK;
-}
-
-int prt_reproject_moments(prt_ctx* c, const prt_temporal_params* p, int32_t W, int32_t H, const prt_camera* cam,
-                          const float* color, const float* normal_depth, const uint32_t* instance,
-                          const prt_camera* prev_cam, const float* history, const float* history_nd,
-                          const uint32_t* history_inst, const float* motion, int32_t count, const float* history_mom,
-                          float* out_rgba, float* out_mom, uint32_t* out_rgb8, uint32_t out_flags) {
-  if (!c || !p || !cam || !color || !normal_depth || !instance || !out_mom || (!out_rgba && !out_rgb8) || W <= 0 ||
-      H <= 0 || W > 16384 || H > 16384)
-    return fail(PRT_ERR_INVALID_ARGUMENT, "bad reproject arguments");
-  if (!sigma_ok(p->depth_tol, true) || !(p->normal_min >= -1.0f && p->normal_min <= 1.0f) ||
-      !std::isfinite(p->max_history) || p->max_history < 1.0f || !sigma_ok(p->clamp_k, true) ||
-      !std::isfinite(p->min_temporal) || p->min_temporal < 1.0f)
-    return fail(PRT_ERR_INVALID_ARGUMENT, "temporal parameters out of range");
-  const int given = (prev_cam ? 1 : 0) + (history ? 1 : 0) + (history_nd ? 1 : 0) + (motion ? 1 : 0) +
-                    (count ? 1 : 0) + (history_mom ? 1 : 0);
-  if (count < 0 || (given != 0 && given != 6) || (given == 0 && history_inst))
-    return fail(PRT_ERR_INVALID_ARGUMENT,
-                "prev_camera, history_rgba, history_normal_depth, motion, count > 0 and history_moments go together");
-  if (out_rgba == color)  // the clamp and the spatial estimate read the neighbours of color_rgba
-    return fail(PRT_ERR_INVALID_ARGUMENT, "out_rgba must not be color_rgba");
-  if (out_rgba && (out_rgba == normal_depth || out_rgba == out_mom ||
-                   (given && (out_rgba == history || out_rgba == history_nd || out_rgba == history_mom))))
-    return fail(PRT_ERR_INVALID_ARGUMENT, "out_rgba must not be an input or out_moments");
-  if (out_mom == color || out_mom == normal_depth ||
-      (given && (out_mom == history_mom || out_mom == history || out_mom == history_nd)))
-    return fail(PRT_ERR_INVALID_ARGUMENT, "out_moments must not be an input");
-  if (out_rgb8 && (out_rgb8 == instance || (history_inst && out_rgb8 == history_inst)))
-    return fail(PRT_ERR_INVALID_ARGUMENT, "out_rgb8 must not be an instance buffer");
-  PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t n = (size_t)W * H, bytes = n * sizeof(float4);
-  const bool dev = (out_flags & PRT_OUT_DEVICE) != 0;
-  const float4* src[4] = {reinterpret_cast<const float4*>(color), reinterpret_cast<const float4*>(normal_depth),
-                          reinterpret_cast<const float4*>(history), reinterpret_cast<const float4*>(history_nd)};
-  const uint32_t* ids[2] = {instance, history_inst};
-  const float4* hmom = reinterpret_cast<const float4*>(history_mom);
-  float4* dst = reinterpret_cast<float4*>(out_rgba);
-  float4* dstm = reinterpret_cast<float4*>(out_mom);
-  uint32_t* dst8 = out_rgb8;
-  if (!dev) {  // host images: staged in context buffers
-    for (int k = 0; k < 4; k++) {
-      if (!src[k]) continue;
-      HIP_TRY(c->rp_in[k].ensure(bytes));
-      HIP_TRY(hipMemcpyAsync(c->rp_in[k].p, src[k], bytes, hipMemcpyHostToDevice, c->stream));
-      src[k] = c->rp_in[k].as<float4>();
-    }
-    for (int k = 0; k < 2; k++) {
-      if (!ids[k]) continue;
-      HIP_TRY(c->rp_ids[k].ensure(n * 4));
-      HIP_TRY(hipMemcpyAsync(c->rp_ids[k].p, ids[k], n * 4, hipMemcpyHostToDevice, c->stream));
-      ids[k] = c->rp_ids[k].as<uint32_t>();
-    }
-    if (hmom) {
-      HIP_TRY(c->rp_mom[0].ensure(bytes));
-      HIP_TRY(hipMemcpyAsync(c->rp_mom[0].p, hmom, bytes, hipMemcpyHostToDevice, c->stream));
-      hmom = c->rp_mom[0].as<float4>();
-    }
-    HIP_TRY(c->rp_mom[1].ensure(bytes));
-    dstm = c->rp_mom[1].as<float4>();
-    if (out_rgba) { HIP_TRY(c->rp_out.ensure(bytes)); dst = c->rp_out.as<float4>(); }
-    if (out_rgb8) { HIP_TRY(c->rp_rgb8.ensure(n * 4)); dst8 = c->rp_rgb8.as<uint32_t>(); }
-  }
-  if (given) {  // the matrices: copied into a pinned staging buffer now, uploaded in stream order (no host wait)
-    const size_t mb = 12 * sizeof(float) * (size_t)count;
-    HIP_TRY(c->rp_motion.ensure(mb));
-    StageSlot* st = nullptr;
-    const int rc = stage_acquire(c, mb, st);
-    if (rc) return rc;
-    std::memcpy(st->p, motion, mb);
-    HIP_TRY(hipMemcpyAsync(c->rp_motion.p, st->p, mb, hipMemcpyHostToDevice, c->stream));
-    const int rr = stage_release(c, *st, c->stream);
-    if (rr) return rr;
-  }
-  MomentsPass Q{};
-  ReprojectPass& R = Q.M.R;
-  R.W = W;
-  R.H = H;
-  R.depth_tol = p->depth_tol;
-  R.normal_min = p->normal_min;
-  R.max_history = p->max_history;
-  make_reproject_pass(R, *cam, prev_cam);
-  R.color = src[0];
-  R.nd = src[1];
-  R.hist = src[2];
-  R.hist_nd = src[3];
-  R.out = dst;
-  R.rgb8 = dst8;
-  Q.M.inst = ids[0];
-  Q.M.hist_inst = ids[1];
-  Q.M.motion = given ? c->rp_motion.as<float4>() : nullptr;
-  Q.M.count = count;
-  Q.hist_mom = hmom;
-  Q.mom = dstm;
-  Q.clamp_k = p->clamp_k;
-  Q.min_temporal = p->min_temporal;
-  HIP_TRY(launch_reproject_moments(c->stream, Q));
-  if (!dev) {
-    if (out_rgba) HIP_TRY(hipMemcpyAsync(out_rgba, dst, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(out_mom, dstm, bytes, hipMemcpyDeviceToHost, c->stream));
-    if (out_rgb8) HIP_TRY(hipMemcpyAsync(out_rgb8, dst8, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-  }
-  return PRT_OK;
-}
-
-int prt_denoise_variance_defaults(prt_denoise_variance_params* out) {
-  if (!out) return fail(PRT_ERR_INVALID_ARGUMENT, "out is NULL");
-  out->iterations = 5;
-  out->normal_power = 3;
-  out->sigma_color = 2.0f;
-  out->sigma_depth = 0.1f;
-  out->sigma_albedo = 0.25f;
-  out->color_decay = 1.0f;
-  out->variance_floor = 1e-6f;
-  return PRT_OK;
-}
-
-int prt_denoise_variance(prt_ctx* c, const prt_denoise_variance_params* p, int32_t W, int32_t H, const float* color,
-                         const float* moments, const float* albedo, const float* normal_depth, float* out_rgba,
-                         float* out_variance, uint32_t* out_rgb8, uint32_t out_flags) {
-  if (!c || !p || !color || !moments || !normal_depth || (!out_rgba && !out_rgb8) || W <= 0 || H <= 0 || W > 16384 ||
-      H > 16384)
-    return fail(PRT_ERR_INVALID_ARGUMENT, "bad denoise arguments");
-  if (p->iterations < 1 || p->iterations > 8 || p->normal_power < 0 || p->normal_power > 7 ||
-      !sigma_ok(p->sigma_color, false) || !sigma_ok(p->sigma_depth, false) || !sigma_ok(p->sigma_albedo, true) ||
-      !sigma_ok(p->color_decay, false) || !sigma_ok(p->variance_floor, false))
-    return fail(PRT_ERR_INVALID_ARGUMENT, "denoise parameters out of range");
-  const bool use_albedo = p->sigma_albedo > 0.0f;
-  if (use_albedo && !albedo) return fail(PRT_ERR_INVALID_ARGUMENT, "albedo is NULL with sigma_albedo > 0");
-  PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t n = (size_t)W * H, bytes = n * sizeof(float4);
-  const bool dev = (out_flags & PRT_OUT_DEVICE) != 0, timed = (out_flags & PRT_OUT_TIMED) != 0;
-  const float4* src[3] = {reinterpret_cast<const float4*>(color), reinterpret_cast<const float4*>(normal_depth),
-                          use_albedo ? reinterpret_cast<const float4*>(albedo) : nullptr};
-  const float4* mom = reinterpret_cast<const float4*>(moments);
-  float4* dst = reinterpret_cast<float4*>(out_rgba);
-  float* dstv = out_variance;
-  uint32_t* dst8 = out_rgb8;
-  if (!dev) {  // host images: staged in context buffers
-    for (int k = 0; k < 3; k++) {
-      if (!src[k]) continue;
-      HIP_TRY(c->dn_in[k].ensure(bytes));
-      HIP_TRY(hipMemcpyAsync(c->dn_in[k].p, src[k], bytes, hipMemcpyHostToDevice, c->stream));
-      src[k] = c->dn_in[k].as<float4>();
-    }
-    HIP_TRY(c->dn_mom.ensure(bytes));
-    HIP_TRY(hipMemcpyAsync(c->dn_mom.p, mom, bytes, hipMemcpyHostToDevice, c->stream));
-    mom = c->dn_mom.as<float4>();
-    if (out_rgba) { HIP_TRY(c->dn_out.ensure(bytes)); dst = c->dn_out.as<float4>(); }
-    if (out_variance) { HIP_TRY(c->dn_var.ensure(n * 4)); dstv = c->dn_var.as<float>(); }
-    if (out_rgb8) { HIP_TRY(c->dn_rgb8.ensure(n * 4)); dst8 = c->dn_rgb8.as<uint32_t>(); }
-  }
-  HIP_TRY(c->dn_geo.ensure(bytes));
-  HIP_TRY(c->dn_pp[0].ensure(bytes));  // (rgb, V): iteration i reads dn_pp[i & 1]
-  if (p->iterations > 1) HIP_TRY(c->dn_pp[1].ensure(bytes));
-  int rc = PRT_OK;
-  if (timed && (rc = dn_event(c, 2))) return rc;
-  HIP_TRY(launch_denoise_var_prep(c->stream, W, H, src[1], src[0], mom, c->dn_geo.as<float4>(),
-                                  c->dn_pp[0].as<float4>()));
-  if (timed && (rc = dn_event(c, 3))) return rc;
-  float sc = p->sigma_color;
-  for (int32_t i = 0; i < p->iterations; i++) {
-    const bool last = i == p->iterations - 1;
-    VarDenoisePass Q{};
-    DenoisePass& P = Q.D;
-    P.W = W;
-    P.H = H;
-    P.step = 1 << i;
-    P.normal_power = p->normal_power;
-    P.sc2 = sc * sc;
-    P.sigma_depth = p->sigma_depth;
-    P.sa2 = p->sigma_albedo * p->sigma_albedo;
-    P.color = c->dn_pp[i & 1].as<float4>();
-    P.geo = c->dn_geo.as<float4>();
-    P.albedo = src[2];
-    P.out = last ? dst : c->dn_pp[(i + 1) & 1].as<float4>();
-    P.rgb8 = last ? dst8 : nullptr;
-    Q.variance_floor = p->variance_floor;
-    Q.restore = last ? src[0] : nullptr;
-    Q.variance = last ? dstv : nullptr;
-    HIP_TRY(launch_denoise_var_pass(c->stream, Q));
-    if (timed && (rc = dn_event(c, 4 + i))) return rc;
-    sc = sc * p->color_decay;
-  }
-  if (timed) c->dn_timed_passes = p->iterations;
-  if (!dev) {
-    if (out_rgba) HIP_TRY(hipMemcpyAsync(out_rgba, dst, bytes, hipMemcpyDeviceToHost, c->stream));
-    if (out_variance) HIP_TRY(hipMemcpyAsync(out_variance, dstv, n * 4, hipMemcpyDeviceToHost, c->stream));
-    if (out_rgb8) HIP_TRY(hipMemcpyAsync(out_rgb8, dst8, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-  }
-  return PRT_OK;
 }
 
 int prt_brdf_probe(prt_ctx* c, int32_t op, int32_t n, const float* in, float* out) {

@@ -22,6 +22,24 @@ def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+def _ptr(a):
+    """The address of a host array; a raw device pointer, None or a ctypes argument as it is."""
+    return a.ctypes.data if isinstance(a, np.ndarray) else a
+
+
+def _images(n, device_out, timed=False, f32=(), u32=(), outs=()):
+    """The images of an image-space call (AOVs, denoisers, reprojections) and its out-flags: (f32 inputs, u32 inputs,
+    outputs, flags).  Host mode: the inputs (arrays or None) as contiguous [n,4] float32 / [n] uint32 arrays, and a
+    fresh zeroed output per (given, columns, dtype) of `outs`: [n,4] for 4 columns, [n] for 1, None for 0.
+    device_out: every image is a raw device pointer and stays as given.  _ptr() makes either the call's argument."""
+    of = (_lib.OUT_DEVICE if device_out else 0) | (_lib.OUT_TIMED if timed else 0)
+    if device_out:
+        return list(f32), list(u32), [o[0] for o in outs], of
+    f32 = [_f32(a).reshape(n, 4) if a is not None else None for a in f32]
+    u32 = [np.ascontiguousarray(a, np.uint32).reshape(n) if a is not None else None for a in u32]
+    return f32, u32, [np.zeros((n, 4) if k == 4 else n, dt) if k else None for _, k, dt in outs], of
+
+
 @dataclass
 class LightTransform:
     """LightTransform (Core/LightTransform.cpp:4-23): position, color, rotation."""
@@ -482,15 +500,9 @@ class Context:
         """(albedo[n,4], normal_depth[n,4]) of the first hit at pixel centres: base colour (w = 1; miss 0) and the
         shading normal as Trace uses it with the hit distance in w (miss 0,0,0,1e30).  The accumulation and the ray
         totals stay as they are.  device_out: albedo / normal_depth are raw device pointers (either may be None)."""
-        n = width * height
-        if not device_out:
-            albedo = np.zeros((n, 4), F32)
-            normal_depth = np.zeros((n, 4), F32)
-            pa, pn = albedo.ctypes.data, normal_depth.ctypes.data
-        else:
-            pa, pn = albedo, normal_depth
-        of = (_lib.OUT_DEVICE if device_out else 0) | (_lib.OUT_TIMED if timed else 0)
-        check(self.L.prt_render_aov(self.h, width, height, flags, pa, pn, of))
+        _, _, (albedo, normal_depth), of = _images(width * height, device_out, timed,
+                                                   outs=((albedo, 4, F32), (normal_depth, 4, F32)))
+        check(self.L.prt_render_aov(self.h, width, height, flags, _ptr(albedo), _ptr(normal_depth), of))
         return albedo, normal_depth
 
     def denoise(self, color, albedo, normal_depth, width, height, params=None, device_out=False, out=None, rgb8=None,
@@ -499,18 +511,9 @@ class Context:
         buffers; returns (out[n,4], rgb8[n]).  device_out: every image is a raw device pointer, out / rgb8 are
         where the results go (either may be None; out may be the same pointer as color) and no host wait happens."""
         dp = params if params is not None else denoise_defaults()
-        n = width * height
-        of = (_lib.OUT_DEVICE if device_out else 0) | (_lib.OUT_TIMED if timed else 0)
-        if not device_out:
-            color, normal_depth = _f32(color).reshape(n, 4), _f32(normal_depth).reshape(n, 4)
-            albedo = _f32(albedo).reshape(n, 4) if albedo is not None else None
-            out = np.zeros((n, 4), F32)
-            rgb8 = np.zeros(n, np.uint32)
-            args = (color.ctypes.data, albedo.ctypes.data if albedo is not None else None, normal_depth.ctypes.data,
-                    out.ctypes.data, rgb8.ctypes.data)
-        else:
-            args = (color, albedo, normal_depth, out, rgb8)
-        check(self.L.prt_denoise(self.h, C.byref(dp), width, height, *args, of))
+        ins, _, (out, rgb8), of = _images(width * height, device_out, timed, (color, albedo, normal_depth),
+                                          outs=((out, 4, F32), (rgb8, 1, np.uint32)))
+        check(self.L.prt_denoise(self.h, C.byref(dp), width, height, *map(_ptr, ins + [out, rgb8]), of))
         return out, rgb8
 
     def denoise_timings(self):
@@ -529,20 +532,13 @@ class Context:
         every image is a raw device pointer, out / rgb8 are where the results go (either may be None; out may be
         color, not a history buffer) and no host wait happens.  Plane projection only (no post-processing)."""
         rp = params if params is not None else reproject_defaults()
-        n = width * height
         cam = _camera_desc(camera)
         prev = C.byref(_camera_desc(prev_camera)) if prev_camera is not None else None
-        if not device_out:
-            imgs = [_f32(a).reshape(n, 4) if a is not None else None
-                    for a in (color, normal_depth, history, history_normal_depth)]
-            out = np.zeros((n, 4), F32)
-            rgb8 = np.zeros(n, np.uint32)
-            pc, pn, ph, pg = (a.ctypes.data if a is not None else None for a in imgs)
-            po, p8 = out.ctypes.data, rgb8.ctypes.data
-        else:
-            pc, pn, ph, pg, po, p8 = color, normal_depth, history, history_normal_depth, out, rgb8
-        check(self.L.prt_reproject(self.h, C.byref(rp), width, height, C.byref(cam), pc, pn, prev, ph, pg, po, p8,
-                                   _lib.OUT_DEVICE if device_out else 0))
+        (c, g, h, hg), _, (out, rgb8), of = _images(
+            width * height, device_out, False, (color, normal_depth, history, history_normal_depth),
+            outs=((out, 4, F32), (rgb8, 1, np.uint32)))
+        check(self.L.prt_reproject(self.h, C.byref(rp), width, height, C.byref(cam),
+                                   *map(_ptr, (c, g, prev, h, hg, out, rgb8)), of))
         return out, rgb8
 
     # -- moving instances in the reprojection (include/prt.h prt_render_aov_ids / prt_reproject_motion)
@@ -551,17 +547,10 @@ class Context:
         """render_aov() with the first hit's instance index per pixel (uint32, a miss 0xFFFFFFFF) from the same
         primary-hit pass: (albedo[n,4], normal_depth[n,4], instance[n]).  device_out: the three are raw device
         pointers (any may be None)."""
-        n = width * height
-        if not device_out:
-            albedo = np.zeros((n, 4), F32)
-            normal_depth = np.zeros((n, 4), F32)
-            instance = np.zeros(n, np.uint32)
-            pa, pn, pi = albedo.ctypes.data, normal_depth.ctypes.data, instance.ctypes.data
-        else:
-            pa, pn, pi = albedo, normal_depth, instance
-        of = (_lib.OUT_DEVICE if device_out else 0) | (_lib.OUT_TIMED if timed else 0)
-        check(self.L.prt_render_aov_ids(self.h, width, height, flags, pa, pn, pi, of))
-        return albedo, normal_depth, instance
+        _, _, outs, of = _images(width * height, device_out, timed,
+                                 outs=((albedo, 4, F32), (normal_depth, 4, F32), (instance, 1, np.uint32)))
+        check(self.L.prt_render_aov_ids(self.h, width, height, flags, *map(_ptr, outs), of))
+        return tuple(outs)
 
     def reproject_motion(self, color, normal_depth, instance, camera, history=None, history_normal_depth=None,
                          prev_camera=None, history_instance=None, motion=None, *, width, height, params=None,
@@ -571,25 +560,15 @@ class Context:
         history, history_normal_depth, prev_camera and motion are all None (a history starts) or all given;
         history_instance is optional (None: taps are not compared by instance).  Returns (out[n,4], rgb8[n])."""
         rp = params if params is not None else reproject_defaults()
-        n = width * height
         cam = _camera_desc(camera)
         prev = C.byref(_camera_desc(prev_camera)) if prev_camera is not None else None
         mo = _f32(motion).reshape(-1, 12) if motion is not None else None
-        pm, count = (mo.ctypes.data, len(mo)) if mo is not None else (None, 0)
-        if not device_out:
-            imgs = [_f32(a).reshape(n, 4) if a is not None else None
-                    for a in (color, normal_depth, history, history_normal_depth)]
-            ids = [np.ascontiguousarray(a, np.uint32).reshape(n) if a is not None else None
-                   for a in (instance, history_instance)]
-            out = np.zeros((n, 4), F32)
-            rgb8 = np.zeros(n, np.uint32)
-            pc, pn, ph, pg, pi, pj = (a.ctypes.data if a is not None else None for a in imgs + ids)
-            po, p8 = out.ctypes.data, rgb8.ctypes.data
-        else:
-            pc, pn, ph, pg, pi, pj, po, p8 = (color, normal_depth, history, history_normal_depth, instance,
-                                              history_instance, out, rgb8)
-        check(self.L.prt_reproject_motion(self.h, C.byref(rp), width, height, C.byref(cam), pc, pn, pi, prev, ph, pg,
-                                          pj, pm, count, po, p8, _lib.OUT_DEVICE if device_out else 0))
+        (c, g, h, hg), (i, hi), (out, rgb8), of = _images(
+            width * height, device_out, False, (color, normal_depth, history, history_normal_depth),
+            (instance, history_instance), ((out, 4, F32), (rgb8, 1, np.uint32)))
+        check(self.L.prt_reproject_motion(
+            self.h, C.byref(rp), width, height, C.byref(cam),
+            *map(_ptr, (c, g, i, prev, h, hg, hi, mo, 0 if mo is None else len(mo), out, rgb8)), of))
         return out, rgb8
 
     # -- luminance moments and the variance-guided filter (include/prt.h prt_reproject_moments / prt_denoise_variance)
@@ -600,27 +579,15 @@ class Context:
         call's moments output and belongs to the all-or-nothing history group; `instance` is always required; `out`
         must not be `color`.  Returns (out[n,4], moments[n,4], rgb8[n]); moments is (m1, m2, variance, 0)."""
         tp = params if params is not None else temporal_defaults()
-        n = width * height
         cam = _camera_desc(camera)
         prev = C.byref(_camera_desc(prev_camera)) if prev_camera is not None else None
         mo = _f32(motion).reshape(-1, 12) if motion is not None else None
-        pm, count = (mo.ctypes.data, len(mo)) if mo is not None else (None, 0)
-        if not device_out:
-            imgs = [_f32(a).reshape(n, 4) if a is not None else None
-                    for a in (color, normal_depth, history, history_normal_depth, history_moments)]
-            ids = [np.ascontiguousarray(a, np.uint32).reshape(n) if a is not None else None
-                   for a in (instance, history_instance)]
-            out = np.zeros((n, 4), F32)
-            moments = np.zeros((n, 4), F32)
-            rgb8 = np.zeros(n, np.uint32)
-            pc, pn, ph, pg, pq, pi, pj = (a.ctypes.data if a is not None else None for a in imgs + ids)
-            po, pmo, p8 = out.ctypes.data, moments.ctypes.data, rgb8.ctypes.data
-        else:
-            pc, pn, ph, pg, pq, pi, pj, po, pmo, p8 = (color, normal_depth, history, history_normal_depth,
-                                                       history_moments, instance, history_instance, out, moments,
-                                                       rgb8)
-        check(self.L.prt_reproject_moments(self.h, C.byref(tp), width, height, C.byref(cam), pc, pn, pi, prev, ph, pg,
-                                           pj, pm, count, pq, po, pmo, p8, _lib.OUT_DEVICE if device_out else 0))
+        (c, g, h, hg, hm), (i, hi), (out, moments, rgb8), of = _images(
+            width * height, device_out, False, (color, normal_depth, history, history_normal_depth, history_moments),
+            (instance, history_instance), ((out, 4, F32), (moments, 4, F32), (rgb8, 1, np.uint32)))
+        check(self.L.prt_reproject_moments(
+            self.h, C.byref(tp), width, height, C.byref(cam),
+            *map(_ptr, (c, g, i, prev, h, hg, hi, mo, 0 if mo is None else len(mo), hm, out, moments, rgb8)), of))
         return out, moments, rgb8
 
     def denoise_variance(self, color, moments, albedo, normal_depth, width, height, params=None, device_out=False,
@@ -629,22 +596,11 @@ class Context:
         (out[n,4], variance[n] or None, rgb8[n]).  device_out: every image is a raw device pointer, out / variance /
         rgb8 are where the results go (out or rgb8 and variance may be None; out may be the same pointer as color)."""
         dp = params if params is not None else denoise_variance_defaults()
-        n = width * height
-        of = (_lib.OUT_DEVICE if device_out else 0) | (_lib.OUT_TIMED if timed else 0)
-        if not device_out:
-            color, moments = _f32(color).reshape(n, 4), _f32(moments).reshape(n, 4)
-            normal_depth = _f32(normal_depth).reshape(n, 4)
-            albedo = _f32(albedo).reshape(n, 4) if albedo is not None else None
-            out = np.zeros((n, 4), F32)
-            variance = np.zeros(n, F32) if want_variance else None
-            rgb8 = np.zeros(n, np.uint32)
-            args = (color.ctypes.data, moments.ctypes.data, albedo.ctypes.data if albedo is not None else None,
-                    normal_depth.ctypes.data, out.ctypes.data, variance.ctypes.data if want_variance else None,
-                    rgb8.ctypes.data)
-        else:
-            args = (color, moments, albedo, normal_depth, out, variance, rgb8)
-        check(self.L.prt_denoise_variance(self.h, C.byref(dp), width, height, *args, of))
-        return out, variance, rgb8
+        ins, _, outs, of = _images(
+            width * height, device_out, timed, (color, moments, albedo, normal_depth),
+            outs=((out, 4, F32), (variance, 1 if want_variance else 0, F32), (rgb8, 1, np.uint32)))
+        check(self.L.prt_denoise_variance(self.h, C.byref(dp), width, height, *map(_ptr, ins + outs), of))
+        return tuple(outs)
 
     def intersect(self, O, D, tmax=None):
         O, D = _f32(O), _f32(D)
