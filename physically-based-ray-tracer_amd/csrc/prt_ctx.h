@@ -17,8 +17,9 @@
 
 namespace prt::host {
 
-// sets the calling thread's prt_last_error text (prt_api.cpp) and returns code
+// sets the calling thread's prt_last_error text (prt_api.cpp) and returns code; the text as it stands
 int fail(int code, const std::string& msg);
+std::string& last_error();
 
 #define HIP_TRY(expr)                                                                        \
   do {                                                                                       \
@@ -282,6 +283,22 @@ int join_flights(prt_ctx* c);
 #define PRT_JOIN(ctx) PRT_TRY(::prt::host::join_flights(ctx))
 int stage_acquire(prt_ctx* c, size_t bytes, StageSlot*& out);
 int stage_release(prt_ctx*, StageSlot& st, hipStream_t s);
+// prt_api.cpp, for the render path: finish the queued frames before resident buffers are overwritten or freed; the
+// bounded RCCL waits; the traversal occupancy and whether the stacks cover the BVH; the HBM spill columns of S; the
+// scene as the kernels get it; the screen pass's parameters; the mark of a frame's read of the instance state
+int drain(prt_ctx* c);
+ncclResult_t rccl_settle(const Rccl* R, ncclComm_t comm, ncclResult_t r);
+int rccl_wait(prt_ctx* c, hipStream_t s, const char* what);
+int occ_for(const prt_ctx* c);
+bool depth_ok(const prt_ctx* c);
+int ensure_spill(prt_ctx* c, SceneDev& S, size_t threads);
+int scene_ready(prt_ctx* c, SceneDev& S);
+PostDev post_params(const prt_ctx* c, int32_t W, int32_t H);
+int record_inst_use(prt_ctx* c, hipStream_t st);
+// prt_api_render.cpp: the context's traversal stack overflow count (waits for the context stream); a shard's tile size
+// and event
+uint64_t diag_overflows(prt_ctx* c, bool* layout_ok = nullptr, bool* wait_ok = nullptr);
+int shard_setup(prt_ctx* c, int32_t tile);
 // prt_api_image.cpp: record timing event k (prt_ctx::dn_ev) on the context stream
 int dn_event(prt_ctx* c, int k);
 

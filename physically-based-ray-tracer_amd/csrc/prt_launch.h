@@ -1,10 +1,12 @@
-// prt_launch.h -- host-side launchers implemented in prt_render.hip.
+// prt_launch.h -- the host-side launchers of the kernel files (prt_render.hip, prt_wave2.hip, prt_defer.hip) and the
+// argument structs they share with the host code.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 
 #include "prt_kernels.h"
+#include "prt_plan.h"
 #include "prt_post.h"
 #include "prt_traverse8.h"
 
@@ -21,12 +23,10 @@ struct LaunchCfg {
   hipStream_t stream;
   int occ;     // persistent traversal waves/SIMD: 7 / 6 / 5 / 4 (9 / 11 / 14 / 18 LDS stack groups)
   uint32_t groups = 1;  // grid divisor: every wavefront grid is 1/groups of the resident blocks (frames in flight:
-                        // the chains' persistent launches co-reside on the SIMDs, prt_api.cpp enqueue_render)
+                        // the chains' persistent launches co-reside on the SIMDs, prt_api_render.cpp enqueue_render)
 };
 
-// wavefront pipeline buffers (SoA over n work items; R/T hold (bounces-1) x n entries)
-constexpr uint32_t kNSub = 32;       // sub-queues per queue (one append counter each)
-constexpr uint32_t kCtrStride = 32;  // words between counters (each on its own 128-B line)
+// wavefront pipeline buffers (SoA over n work items; R/T hold (bounces-1) x n entries; layout: prt_plan.h)
 struct WaveBufs {
   uint32_t n;       // items of this call
   uint32_t base;    // first item of the state arrays within the call (0)
@@ -34,7 +34,7 @@ struct WaveBufs {
   uint32_t scap;    // capacity of one shadow sub-queue (4 x qcap)
   uint32_t* seed;
   uint32_t* info;   // depth | path << 8 | status << 16 | nee kind << 20
-  uint32_t* rinfo;  // merged pipeline: what k_resolve2 finishes (depth | path << 8 | status << 16 | kind << 20)
+  uint32_t* rinfo;  // what the resolve of the next launch finishes (depth | path << 8 | status << 16 | kind << 20)
   float4* ro;
   float4* rd;
   float4* R;
@@ -51,7 +51,7 @@ struct WaveBufs {
   uint32_t* shq;    // shadow queue: light << 29 | visibility index (prt_wave2.hip shadow_of)
   float4* hp;       // the hit point I of the item's last shading (its shadow rays' origin before the offset)
   uint32_t* ctr;    // [iteration][path|shadow][sub-queue] counters, kCtrStride apart
-  // extensions (area light / dielectric instances; merged pipeline only): vis holds 5 x n bytes, the area
+  // extensions (area light / dielectric instances; Pipeline::Ext only): vis holds 5 x n bytes, the area
   // light's shadow ray writes byte 4 * n + item
   float4* na;       // area-light NEE contribution before visibility
   uint32_t* dst;    // dielectric DFS state: bits 0-7 dielectric level, 8-15 refraction started,
@@ -77,7 +77,7 @@ struct WaveBufs {
   // light-visibility record (prt_wave2.hip): per tile-map entry, indexed like phit, what the shadow rays from the
   // entry's fixed primary hit towards the six light-class lights found (8 bytes: byte l for light l; 0 unknown,
   // 1 occluded, 2 unoccluded).  Null unless the pass runs with kPrimReuse and the record belongs to phit and to
-  // the lights' positions (prt_api.cpp); one copy per wavefront state
+  // the lights' positions (prt_api_render.cpp); one copy per wavefront state
   uint2* lvis;
   uint32_t lslot;          // the iteration whose shadow counter counts the shadow rays not queued (iters + 1): those
                            // answered from lvis and the dead ones
@@ -87,21 +87,9 @@ struct WaveBufs {
 };
 static_assert(sizeof(WaveBufs) % 8 == 0 && offsetof(WaveBufs, dead) + 4 == sizeof(WaveBufs),
               "dead fills WaveBufs' tail padding");
-enum : int32_t { kPrimTrace = 0, kPrimDense = 1, kPrimReuse = 2 };
-constexpr uint32_t kParts = 8;  // XCD parts of a traversal launch's live range, one fetch counter each (prt_queue.h)
-constexpr int kMaxIters = 128;  // wavefront iterations per call: bounces <= 64 (AA) / 6 with dielectrics (AA)
 #ifdef PRT_LANE_STATS
 void lane_stats_dump();  // diagnostic build: prints and clears the traversal lane counters (prt_wave2.hip)
 #endif
-// wavefront iterations of one call: one per path segment, paths x bounces; with dielectric instances a path
-// is a binary tree walked depth first (one segment per iteration), at most 2^bounces - 1 segments per path
-inline uint32_t wave_iters(bool dielectric, int bounces, uint32_t flags, bool merge = false) {
-  const uint32_t paths = (flags & 1u) ? 2u : 1u;  // PRT_FLAG_AA: two camera paths per reference frame
-  // merged: path 2's first segment is shaded in the iteration path 1 ends in (its primary hit traced up front)
-  if (merge && paths == 2 && bounces > 0) return 2u * (uint32_t)bounces - 1u;
-  if (!dielectric) return paths * (uint32_t)bounces;
-  return bounces > 8 ? 0xFFFFFFFFu : paths * ((1u << bounces) - 1u);  // dst holds 4 bits per level for 8 levels
-}
 constexpr int kTlWaves = 256 * 4 * 8;  // timeline records per traversal launch (max persistent grid)
 struct WaveTimers {
   hipEvent_t ev[4 * (kMaxIters + 1)];
@@ -110,13 +98,15 @@ struct WaveTimers {
 
 hipError_t launch_wave_init(const LaunchCfg& c, const SceneDev& S, const TraceArgs& A, const TileMap& M,
                             const WaveBufs& B, float4* out);
-// merged pipeline (prt_wave2.hip): iteration `it` (0..iters) after launch_wave_init -- one traversal launch for
-// P(it) closest + S(it-1) any-hit, then resolve / miss / shade.
-// defer (plain pipeline only: no extensions, render mode 0, not merged): the pass's resolve is deferred to one launch
-// behind the last traversal (prt_defer.hip k_resolve_pass).  B's rinfo / ne / nb / nk / vis / T then point at plane 0
-// of `iters` record planes of B.n entries each (plane i at i * B.n); B.R is not used
+// launch `it` (0..iters) of a pass after launch_wave_init (prt_wave2.hip): one traversal launch for P(it) closest +
+// S(it-1) any-hit, then resolve / miss / shade -- the kernels wave_schedule (prt_plan.h) names for the plan's pipeline.
+// lrec: the pass runs with kPrimReuse and holds a light-visibility record (B.lvis).
+// Pipeline::PlainDeferred: the pass's resolve is one launch behind the last traversal (prt_defer.hip k_resolve_pass).
+// B's rinfo / ne / nb / nk / vis / T then point at plane 0 of `iters` record planes of B.n entries each (plane i at
+// i * B.n); B.R is not used
 hipError_t launch_wave2_iter(const LaunchCfg& c, const SceneDev& S, const TraceArgs& A, const TileMap& M,
-                             const WaveBufs& B, float4* out, WaveTimers* tm, uint32_t it, bool defer = false);
+                             const WaveBufs& B, float4* out, WaveTimers* tm, const WavePlan& P, bool lrec,
+                             uint32_t it);
 // ... whose shading (into the record plane B points at) and resolve launches prt_defer.hip holds
 void launch_shade2d(hipStream_t s, unsigned grid, const SceneDev& S, const TraceArgs& A, const TileMap& M,
                     const WaveBufs& B, uint32_t it, bool i0);

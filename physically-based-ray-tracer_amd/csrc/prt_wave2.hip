@@ -22,20 +22,22 @@
 //                    queued into P(i) (a subset of P(i-1)), this iteration's misses (i = 0: k_miss2 over P(0))
 //     k_shade2(i)    the sky radiance of the misses (no extensions), hit attributes, NEE set-up -> S(i), BRDF
 //                    sample or path-2 start -> P(i+1)
+// Which instantiation each stage of launch i is, for each of the five pipelines, is wave_schedule (prt_plan.h); which
+// pipeline a call takes is plan_render there.  launch_wave2_iter below only launches what they name.
 //
 // Hazards (all kernels on one stream): P(i+1) reuses P(i-1)'s buffer after the resolve (i) read it;
 // S(i) reuses S(i-1)'s buffer after k_trace2(i) read it; the resolve (i) reads ne/nb/nk/vis/R/T of an item for
 // iteration i-1 before it (misses) or k_shade2(i) (hits) overwrites them; rinfo keeps iteration i-1's status
 // (and whether the item was queued) while info already holds the state of the queued next ray.
 //
-// Deferred resolve (plain pipeline: no extensions, render mode 0, not merged; prt_defer.hip).  Nothing downstream needs
-// a path's radiance before k_accumulate, and an item is shaded in consecutive iterations from 0, so a pass whose record
-// planes fit the budget (prt_api.cpp defer_for) launches no k_res2d: the host hands k_shade2d(i) plane i of rinfo / ne /
-// nb / nk / vis / T (throughput per iteration, not per depth) and k_trace2(i) the vis of plane i - 1, and one
+// Deferred resolve (Pipeline::PlainDeferred; prt_defer.hip).  Nothing downstream needs a path's radiance before
+// k_accumulate, and an item is shaded in consecutive iterations from 0, so a pass whose record planes fit the budget
+// (prt_plan.h plan_render) launches no k_res2d: the host hands k_shade2d(i) plane i of rinfo / ne / nb / nk / vis / T
+// (throughput per iteration, not per depth) and k_trace2(i) the vis of plane i - 1, and one
 // k_resolve_pass behind the last traversal launch walks every item's planes bottom-up.  R is not used; the hazards on
 // ne / nb / nk / vis / T above are gone with the shared record; k_trace2 is the same kernel with another pointer.
 //
-// Primary-hit reuse (plain and merged pipeline: no extensions, render mode 0; WaveBufs::phit / pmode).  Path 1 of
+// Primary-hit reuse (the plain and merged pipelines; WaveBufs::phit / pmode).  Path 1 of
 // a pixel starts at the pixel centre (only path 2 is jittered, :61), so its primary ray is the same in every
 // reference frame of a call and in every later call while camera, tile map, scene and instances stay put.  Its
 // hit is kept in phit, one record per tile-map entry, and P(0) itself is never traced:
@@ -72,7 +74,7 @@
 // frames of a pass shade before its resolve runs, so a pass never reads what it writes).  Two frames of a pixel may
 // store the same bytes in one launch, always with the same values (the pattern of vis8).  Each wavefront state owns
 // its record; the host clears it (hipMemsetAsync on the state's stream, before k_wave_init) when a dense pass has
-// rewritten phit since it was learned or the light positions differ (prt_api.cpp enqueue_render_body).
+// rewritten phit since it was learned or the light positions differ (prt_api_render.cpp enqueue_render_body).
 //
 // Dead shadow rays (every shading form but the two under the record above; B.dead, the PRT_DEAD_SHADOW level).  A
 // light-class shadow ray is dead when its visibility answer is multiplied by exactly zero: PRT_FLAG_LIGHTED is off,
@@ -683,6 +685,7 @@ void launch_t2(const LaunchCfg& c, const SceneDev& S, const WaveBufs& B, uint32_
 }
 // persistent traversal occupancy (waves/SIMD) -> LDS stack groups per lane; a BVH deeper than the 18 LDS
 // groups at 4 waves/SIMD hold runs the 4-wave form with the HBM spill columns (S.spill)
+// DENSE: the dense primary pass of iteration 0 (Kernel::Trace2Dense), an instantiation of its own
 template <bool DENSE>
 static void launch_trace2_t(const LaunchCfg& c, const SceneDev& S, const WaveBufs& B, uint32_t it, uint32_t iters) {
   if (S.spill) {
@@ -697,23 +700,20 @@ static void launch_trace2_t(const LaunchCfg& c, const SceneDev& S, const WaveBuf
   else if (c.occ == 5) launch_t2<14, 5, 32, DENSE>(c, S, B, it, iters);
   else launch_t2<18, 4, 32, DENSE>(c, S, B, it, iters);
 }
-// (the dense primary pass of iteration 0 is an instantiation of its own, k_trace2)
-static void launch_trace2(const LaunchCfg& c, const SceneDev& S, const WaveBufs& B, uint32_t it, uint32_t iters) {
-  if (it == 0 && B.pmode == kPrimDense) launch_trace2_t<true>(c, S, B, it, iters);
-  else launch_trace2_t<false>(c, S, B, it, iters);
-}
 
 // producer grids (the kernels that append to the sub-queues: k_wave_init, the shading kernels): a multiple of kNSub,
 // so that block b appends to sub-queue b % kNSub exactly the chunks c == b (mod kNSub) it consumes -- the bound
-// ensure_wave sizes each sub-queue by (qcap).  1/groups of the resident blocks, rounded down to that multiple
+// wave_layout sizes each sub-queue by (qcap).  1/groups of the resident blocks, rounded down to that multiple
 __host__ inline unsigned producer_blocks(const LaunchCfg& c) {
   const unsigned g = 256u * 4u / c.groups;
   return g < kNSub ? kNSub : g - g % kNSub;
 }
 
-// one iteration of the merged pipeline: trace P(it) + S(it - 1), resolve P(it - 1), miss + shade P(it)
+// launch `it` of a pass: trace P(it) + S(it - 1), resolve P(it - 1), miss + shade P(it), by the kernels wave_schedule
+// (prt_plan.h) names for the plan's pipeline
 hipError_t launch_wave2_iter(const LaunchCfg& c, const SceneDev& S, const TraceArgs& A, const TileMap& M,
-                             const WaveBufs& B, float4* out, WaveTimers* tm, uint32_t it, bool defer) {
+                             const WaveBufs& B, float4* out, WaveTimers* tm, const WavePlan& P, bool lrec,
+                             uint32_t it) {
   if (B.n == 0) return hipSuccess;
   const unsigned gprod = producer_blocks(c);
   // k_shade2 over 4x the resident blocks when a call holds >= 2^21 items: the extra blocks queue behind the
@@ -722,30 +722,27 @@ hipError_t launch_wave2_iter(const LaunchCfg& c, const SceneDev& S, const TraceA
 #ifndef PRT_SHADE_GRID
   const unsigned gshade = B.n >= (1u << 21) ? 4u * gprod : gprod;
 #else
-  // the sub-queue bound of ensure_wave (qcap) holds only when block b appends to sub-queue b % kNSub for
+  // the sub-queue bound of wave_layout (qcap) holds only when block b appends to sub-queue b % kNSub for
   // chunks c == b (mod kNSub), i.e. for grids that are multiples of kNSub
   static_assert(PRT_SHADE_GRID % kNSub == 0, "PRT_SHADE_GRID must be a multiple of kNSub");
   const unsigned gshade = PRT_SHADE_GRID;
 #endif
-  const uint32_t iters = wave_iters(S.has_diel != 0, A.bounces, A.flags, B.merge != 0);
+  const uint32_t iters = P.iters;
+  const Schedule k = wave_schedule(P.pipeline, lrec, B.pmode, it, iters);
   if (tm) (void)hipEventRecord(tm->ev[4 * it + 0], c.stream);
-  // primary-hit reuse with a current phit: launch 0 of the plain pipeline has nothing to trace (no shadow rays yet,
-  // no path-2 primaries) and is not launched; its two timer events are still recorded, back to back (read_stats
-  // reads a pair per iteration; the launch shows as ~0 ms and leaves no PRT_DEBUG_QUEUES timeline record)
   // deferred resolve (prt_defer.hip): B's record pointers are plane 0.  This launch's shading gets plane `it`; its
   // traversal gets vis of plane it - 1, whose bytes the shadow entries of S(it - 1) index (shadow_vis)
   WaveBufs Bt = B, Bs = B;
-  if (defer) {
+  if (P.defer()) {
     if (it > 0) Bt.vis = B.vis + (size_t)(it - 1u) * B.n;
     const size_t o = (size_t)it * B.n;
     Bs.rinfo += o; Bs.ne += o; Bs.nb += o; Bs.nk += o; Bs.vis += o; Bs.T += o;
   }
-  if (!(it == 0 && B.pmode == kPrimReuse && !B.merge)) launch_trace2(c, S, Bt, it, iters);
+  // a launch with nothing to trace (Kernel::None) still records its two timer events, back to back (read_stats reads a
+  // pair per iteration; the launch shows as ~0 ms and leaves no PRT_DEBUG_QUEUES timeline record)
+  if (k.trace == Kernel::Trace2Dense) launch_trace2_t<true>(c, S, Bt, it, iters);
+  else if (k.trace == Kernel::Trace2) launch_trace2_t<false>(c, S, Bt, it, iters);
   if (tm) (void)hipEventRecord(tm->ev[4 * it + 1], c.stream);
-  const bool ext = (S.area || S.has_diel) && A.mode == 0;
-  // the misses' sky radiance: by k_shade2<false> itself, or (extensions: the area light can turn a hit into a miss
-  // first; debug render modes) by k_miss2 / k_resmiss2 before the shading
-  const uint32_t sep_miss = (ext || A.mode != 0) ? 1u : 0u;
 #ifndef PRT_RES_GRID
   const unsigned gres = gprod;
 #else
@@ -753,36 +750,35 @@ hipError_t launch_wave2_iter(const LaunchCfg& c, const SceneDev& S, const TraceA
 #endif
   // the dense resolves over 2x the resident producer blocks (8 waves/SIMD), at most one chunk per block
   const unsigned gdense = std::min<unsigned>(2u * gprod, (B.n + kBlock - 1) / kBlock);
-  // iteration 0 of a kPrimReuse pass that holds a light-visibility record uses it (shading) and launch 1 adds to it
-  // (resolve): the instantiations of their own
-  const bool lrec = B.pmode == kPrimReuse && B.lvis != nullptr && !ext && A.mode == 0;
-  if (defer) {  // one resolve per pass, behind the last traversal launch
-    if (it == iters) launch_resolve_pass(c.stream, gdense, S, A, B, iters, out, lrec);
-  } else if (it > 0 && B.merge) {
-    if (lrec && it == 1) hipLaunchKernelGGL(k_res2md<true>, dim3(gdense), dim3(kBlock), 0, c.stream, S, A, B, out);
-    else hipLaunchKernelGGL(k_res2md<false>, dim3(gdense), dim3(kBlock), 0, c.stream, S, A, B, out);
-  } else if (it > 0 && !ext && !sep_miss) {
-    if (lrec && it == 1) hipLaunchKernelGGL(k_res2d<true>, dim3(gdense), dim3(kBlock), 0, c.stream, S, A, B, out);
-    else hipLaunchKernelGGL(k_res2d<false>, dim3(gdense), dim3(kBlock), 0, c.stream, S, A, B, out);
-  } else if (it > 0) {  // resolve of P(it - 1) (+ misses of P(it)), one pass
-    if (ext) hipLaunchKernelGGL(k_resmiss2<true>, dim3(gres), dim3(kBlock), 0, c.stream, S, A, B, it, iters, sep_miss,
-                                out);
-    else hipLaunchKernelGGL(k_resmiss2<false>, dim3(gres), dim3(kBlock), 0, c.stream, S, A, B, it, iters, sep_miss,
-                            out);
-  } else if (sep_miss) {
-    if (ext) hipLaunchKernelGGL(k_miss2<true>, dim3(gprod), dim3(kBlock), 0, c.stream, S, A, B, it);
-    else hipLaunchKernelGGL(k_miss2<false>, dim3(gprod), dim3(kBlock), 0, c.stream, S, A, B, it);
+  // (the cases stand in the order this file has always first named the instantiations in: that order places them in
+  // the code object, and their machine code holds offsets relative to that place)
+#define PRT_LAUNCH(kernel, grid, ...) hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, c.stream, __VA_ARGS__)
+  switch (k.resolve) {
+    case Kernel::Res2mdLearn: PRT_LAUNCH(k_res2md<true>, gdense, S, A, B, out); break;
+    case Kernel::Res2md: PRT_LAUNCH(k_res2md<false>, gdense, S, A, B, out); break;
+    case Kernel::Res2dLearn: PRT_LAUNCH(k_res2d<true>, gdense, S, A, B, out); break;
+    case Kernel::Res2d: PRT_LAUNCH(k_res2d<false>, gdense, S, A, B, out); break;
+    case Kernel::ResolvePassLearn: launch_resolve_pass(c.stream, gdense, S, A, B, iters, out, true); break;
+    case Kernel::ResolvePass: launch_resolve_pass(c.stream, gdense, S, A, B, iters, out, false); break;
+    // the misses' sky radiance in a pass of their own (misses = 1), from launch 1 on behind the resolve of P(it - 1)
+    case Kernel::ResMiss2Ext: PRT_LAUNCH(k_resmiss2<true>, gres, S, A, B, it, iters, 1u, out); break;
+    case Kernel::ResMiss2: PRT_LAUNCH(k_resmiss2<false>, gres, S, A, B, it, iters, 1u, out); break;
+    case Kernel::Miss2Ext: PRT_LAUNCH(k_miss2<true>, gprod, S, A, B, it); break;
+    case Kernel::Miss2: PRT_LAUNCH(k_miss2<false>, gprod, S, A, B, it); break;
+    default: assert(k.resolve == Kernel::None);
   }
-  if (it < iters) {
-    const bool i0 = it == 0 && lrec;
-    if (B.merge && i0) hipLaunchKernelGGL(k_shade2m<true>, dim3(gshade), dim3(kBlock), 0, c.stream, S, A, M, B, it);
-    else if (B.merge) hipLaunchKernelGGL(k_shade2m<false>, dim3(gshade), dim3(kBlock), 0, c.stream, S, A, M, B, it);
-    else if (A.mode != 0) hipLaunchKernelGGL(k_shade2_debug, dim3(gprod), dim3(kBlock), 0, c.stream, S, A, M, B, it);
-    else if (ext) hipLaunchKernelGGL(k_shade2<true>, dim3(gshade), dim3(kBlock), 0, c.stream, S, A, M, B, it);
-    else if (defer) launch_shade2d(c.stream, gshade, S, A, M, Bs, it, i0);
-    else if (i0) hipLaunchKernelGGL((k_shade2<false, true>), dim3(gshade), dim3(kBlock), 0, c.stream, S, A, M, B, it);
-    else hipLaunchKernelGGL(k_shade2<false>, dim3(gshade), dim3(kBlock), 0, c.stream, S, A, M, B, it);
+  switch (k.shade) {
+    case Kernel::Shade2mLearn: PRT_LAUNCH(k_shade2m<true>, gshade, S, A, M, B, it); break;
+    case Kernel::Shade2m: PRT_LAUNCH(k_shade2m<false>, gshade, S, A, M, B, it); break;
+    case Kernel::Shade2Debug: PRT_LAUNCH(k_shade2_debug, gprod, S, A, M, B, it); break;
+    case Kernel::Shade2Ext: PRT_LAUNCH(k_shade2<true>, gshade, S, A, M, B, it); break;
+    case Kernel::Shade2dLearn: launch_shade2d(c.stream, gshade, S, A, M, Bs, it, true); break;
+    case Kernel::Shade2d: launch_shade2d(c.stream, gshade, S, A, M, Bs, it, false); break;
+    case Kernel::Shade2Learn: PRT_LAUNCH((k_shade2<false, true>), gshade, S, A, M, B, it); break;
+    case Kernel::Shade2: PRT_LAUNCH(k_shade2<false>, gshade, S, A, M, B, it); break;
+    default: assert(k.shade == Kernel::None);
   }
+#undef PRT_LAUNCH
   if (tm) tm->iters = iters + 1;
   return hipGetLastError();
 }

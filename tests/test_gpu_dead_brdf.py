@@ -10,7 +10,6 @@ shadow_rays) and ray_totals() against a fresh context that renders the same call
 asserted throughout: default > level 1 > 0 == level 0 shows that the new rule engages on top of the old one.
 
 Shapes as test_gpu_dead_shadow.py: 96x64 and 70x45, bounces 3, spp 4 = two reference frames per call."""
-import contextlib
 import dataclasses
 
 import numpy as np
@@ -19,6 +18,7 @@ import pytest
 import prt
 from helpers import gpu_scene
 from prt import _lib, scenes, tiles
+from wave_env import contexts, env_or_unset as _env
 
 pytestmark = pytest.mark.gpu
 
@@ -28,29 +28,8 @@ DEFAULT = _lib.FLAGS_DEFAULT
 LEVELS = (None, "1", "0")  # the contexts of a test, in this order: default (both rules), contribution rule, off
 
 
-@contextlib.contextmanager
-def _env(monkeypatch, **kv):
-    """Environment switches for the calls inside the block (the library reads them per call); None leaves unset."""
-    for k, v in kv.items():
-        if v is None:
-            monkeypatch.delenv(k, raising=False)
-        else:
-            monkeypatch.setenv(k, v)
-    try:
-        yield
-    finally:
-        for k in kv:
-            monkeypatch.delenv(k, raising=False)
-
-
-@contextlib.contextmanager
 def _contexts(n=3):
-    cs = [prt.Context(0) for _ in range(n)]
-    try:
-        yield cs
-    finally:
-        for c in cs:
-            c.close()
+    return contexts(n)
 
 
 def _call(c, W, H, spp, fi, **kw):

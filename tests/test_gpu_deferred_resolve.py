@@ -8,7 +8,6 @@ is of a chain with itself.
 
 PRT_MERGE=0 throughout the deferred cases: calls this small take the merged pipeline by default, which keeps its
 per-iteration resolve.  Shapes 96x64 and 70x45, spp 4."""
-import contextlib
 import dataclasses
 
 import numpy as np
@@ -17,6 +16,7 @@ import pytest
 import prt
 from helpers import gpu_scene
 from prt import _lib, scenes, tiles
+from wave_env import contexts, env_or_unset as _env
 
 pytestmark = pytest.mark.gpu
 
@@ -25,29 +25,8 @@ MODES = (None, "0")  # PRT_DEFER_RESOLVE of the two contexts of a test: default,
 DEFERRED, PER_ITERATION = 3, 2
 
 
-@contextlib.contextmanager
-def _env(monkeypatch, **kv):
-    """Environment switches for the calls inside the block (the library reads them per call); None leaves unset."""
-    for k, v in kv.items():
-        if v is None:
-            monkeypatch.delenv(k, raising=False)
-        else:
-            monkeypatch.setenv(k, v)
-    try:
-        yield
-    finally:
-        for k in kv:
-            monkeypatch.delenv(k, raising=False)
-
-
-@contextlib.contextmanager
 def _contexts(n=2):
-    cs = [prt.Context(0) for _ in range(n)]
-    try:
-        yield cs
-    finally:
-        for c in cs:
-            c.close()
+    return contexts(n)
 
 
 def _call(c, W, H, spp, fi, bounces=3, **kw):

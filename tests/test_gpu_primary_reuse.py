@@ -9,7 +9,6 @@ asserted throughout: without them the comparisons would pass vacuously if the st
 Sizes: 96x64 and 70x45.  prt_render cuts the image into 8x8 blocks (70x45: 72x48 entries, 306 of them padding,
 and partly filled waves at the right and bottom edges), prt_render_tiles into 32-pixel tiles (70x45: 96x64
 entries).  bounces 3; spp 4 is two reference frames per call, spp 6 three."""
-import contextlib
 
 import numpy as np
 import pytest
@@ -18,6 +17,7 @@ import oracle
 import prt
 from helpers import RMSE_TOL, gpu_scene, rmse
 from prt import _lib, scenes, tiles
+from wave_env import contexts, env as _env
 
 pytestmark = pytest.mark.gpu
 
@@ -25,26 +25,8 @@ B = 3
 SIZES = [(96, 64), (70, 45)]
 
 
-@contextlib.contextmanager
-def _env(monkeypatch, **kv):
-    """Environment switches for the calls inside the block (the library reads them per call)."""
-    for k, v in kv.items():
-        monkeypatch.setenv(k, v)
-    try:
-        yield
-    finally:
-        for k in kv:
-            monkeypatch.delenv(k, raising=False)
-
-
-@contextlib.contextmanager
 def _contexts(n=2):
-    cs = [prt.Context(0) for _ in range(n)]
-    try:
-        yield cs
-    finally:
-        for c in cs:
-            c.close()
+    return contexts(n)
 
 
 def _call(c, W, H, spp, fi, **kw):

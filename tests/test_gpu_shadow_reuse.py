@@ -10,7 +10,6 @@ record), call 2 learns (all its frames shade before any answer is known), call 3
 
 Shapes as test_gpu_primary_reuse.py: 96x64 and 70x45, bounces 3; spp 4 is two reference frames per call, spp 6
 three."""
-import contextlib
 import dataclasses
 
 import numpy as np
@@ -19,6 +18,7 @@ import pytest
 import prt
 from helpers import gpu_scene
 from prt import _lib, scenes, tiles
+from wave_env import contexts, env as _env
 
 pytestmark = pytest.mark.gpu
 
@@ -28,26 +28,8 @@ EPS = np.float32(0.01)  # kEpsilon (prt_math.h)
 NONSTOCH = _lib.FLAGS_DEFAULT & ~_lib.FLAG_STOCHASTIC
 
 
-@contextlib.contextmanager
-def _env(monkeypatch, **kv):
-    """Environment switches for the calls inside the block (the library reads them per call)."""
-    for k, v in kv.items():
-        monkeypatch.setenv(k, v)
-    try:
-        yield
-    finally:
-        for k in kv:
-            monkeypatch.delenv(k, raising=False)
-
-
-@contextlib.contextmanager
 def _contexts(n=2):
-    cs = [prt.Context(0) for _ in range(n)]
-    try:
-        yield cs
-    finally:
-        for c in cs:
-            c.close()
+    return contexts(n)
 
 
 def _call(c, W, H, spp, fi, **kw):
