@@ -1,6 +1,6 @@
 // prt_defer.hip -- the deferred resolve of the plain wavefront pipeline (no extensions, render mode 0):
-// the shading forms that fill one record plane per iteration and the one resolve launch per pass.  Its own translation
-// unit: the kernels of prt_wave2.hip keep their machine code.
+// the shading form that fills one record plane per iteration and the one resolve launch per pass, both built from
+// prt_shade2.h's shared pieces (shade2_body; resolve_segment, pixel_value).  Its own translation unit.
 #include "prt_shade2.h"
 
 namespace prt {
@@ -8,8 +8,7 @@ namespace prt {
 // ---- shading of P(iter) into the iteration's record plane: k_shade2<false, I0> with the throughput in the plane
 template <bool I0>
 __global__ void __launch_bounds__(kBlock, I0 ? 4 : 1) k_shade2d(SceneDev S, TraceArgs A, TileMap M, WaveBufs B, uint32_t iter) {
-  constexpr bool EXT = false, DEFER = true;
-#include "prt_shade2_body.inc"
+  shade2_body<false, I0, true>(S, A, M, B, iter);
 }
 
 // ---- deferred resolve (plain pipeline, no extensions, render mode 0): the pass's paths resolved once,
@@ -17,25 +16,10 @@ __global__ void __launch_bounds__(kBlock, I0 ? 4 : 1) k_shade2d(SceneDev S, Trac
 // its records into plane i (rinfo / ne / nb / nk / vis / T of B point at plane 0; plane i lies i * n entries on), and
 // an item is shaded in consecutive iterations from 0: path 1's segments, then (kRiQueued at path 1's end) path 2's.
 // A lane follows that chain through the rinfo planes to each path's last segment and walks back from there: the last
-// segment's resolved value is L, every earlier one gives L = nee_resolve(record k) + L * T_k -- resolve_item<false>'s
-// expressions in its order, the (result, throughput) stack never stored.  Path 1's radiance stays in registers.
+// segment's resolved value is L, every earlier one gives L = resolve_segment(record k) + L * T_k -- what resolve_item
+// computes, in its order, the (result, throughput) stack never stored.  Path 1's radiance stays in registers.
 // Planes behind an item's last iteration hold an earlier pass's records and are never read; an item without a pixel
 // (rinfo 0 from k_wave_init, which wrote its frame entry) is skipped.
-// one segment's value: ne (a miss's end value, or a hit's emissive term where kRiEmissive) through nee_resolve
-__device__ __forceinline__ V3 resolve_segment(const SceneDev& S, const WaveBufs& B, size_t e, uint32_t ri, uint32_t fl) {
-  const uint32_t status = (ri >> 16) & 3u, kind = (ri >> 20) & 3u;
-  const bool nee = status == kStNeeEnd || status == kStNeeCont;
-  const float4 ne = (!nee || (ri & kRiEmissive)) ? B.ne[e] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  V3 L = v3(ne.x, ne.y, ne.z);
-  if (nee) {
-    const float4 nb = B.nb[e], nk = B.nk[e];
-    const uint32_t vw = B.vis[e];
-    const uint32_t vis = ((vw & 0xFFu) ? 1u : 0u) | ((vw & 0xFF00u) ? 2u : 0u) | ((vw & 0xFF0000u) ? 4u : 0u) |
-                         ((vw & 0xFF000000u) ? 8u : 0u);
-    L = nee_resolve(S, (int)kind, vis, L, v3(nb.x, nb.y, nb.z), nk, fl);
-  }
-  return L;
-}
 // the path whose segments are the iterations first..last (rl = rinfo of `last`), bottom-up
 __device__ __forceinline__ V3 resolve_path(const SceneDev& S, const WaveBufs& B, uint32_t item, uint32_t first,
                                            uint32_t last, uint32_t rl, uint32_t fl) {
@@ -67,16 +51,16 @@ __global__ void __launch_bounds__(kBlock, 8) k_resolve_pass(SceneDev S, TraceArg
       if (r & kRiLearn) lvis_learn(B, item, r);
     }
     const uint32_t e1 = path_end(B, item, iters, 0u, r);
-    V3 L = resolve_path(S, B, item, 0u, e1, r, fl);
+    const V3 L1 = resolve_path(S, B, item, 0u, e1, r, fl);
+    V3 L = L1;
     if (fl & kAA) {  // path 2 starts in the iteration after path 1's end (start_path2)
       if (!(r & kRiQueued) || e1 + 1u >= iters) continue;
       r = B.rinfo[(size_t)(e1 + 1u) * B.n + item];
       const uint32_t e2 = path_end(B, item, iters, e1 + 1u, r);
-      const V3 L2 = resolve_path(S, B, item, e1 + 1u, e2, r, fl);
-      L = 0.5f * (L + L2);                                                                 // :65
+      L = resolve_path(S, B, item, e1 + 1u, e2, r, fl);
     }
-    if (fl & kGamma) L = v3(sqrtf(L.x), sqrtf(L.y), sqrtf(L.z));                          // :73-79
-    out[item] = make_float4(L.x, L.y, L.z, B.s1[item].w);
+    const V3 res = pixel_value(L1, L, fl);
+    out[item] = make_float4(res.x, res.y, res.z, B.s1[item].w);
   }
 }
 

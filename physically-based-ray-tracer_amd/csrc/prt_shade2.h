@@ -1,6 +1,12 @@
-// prt_shade2.h -- the shading stage of the wavefront path tracer (prt_wave2.hip): k_shade2 and what it shares with the
-// misses' pass and the resolves.  A header so that the deferred-resolve forms are instantiated in a translation unit
-// of their own (prt_defer.hip) and the kernels of prt_wave2.hip keep their machine code.
+// prt_shade2.h -- what the wavefront pipelines (prt_wave2.hip, prt_defer.hip) share on the device, stated once:
+//   shade_miss / shade_hit      the shading of one path segment: every shading kernel (k_shade2, k_shade2d, both
+//                               passes of k_shade2m) calls them with its own record index, throughput index and ray
+//   shade2_body                 the chunk loop of k_shade2 and k_shade2d around them
+//   resolve_segment, vis_mask   the resolve of one segment (the deferred pass's resolve_path; the per-iteration
+//                               resolve_item keeps the expressions written out, for speed, and shares vis_mask)
+//   pixel_value, finish_path    the end of a path: AA average, gamma, frame write
+// and k_miss2 and the light-visibility record's helpers.  A header so that the deferred-resolve forms are instantiated
+// in a translation unit of their own (prt_defer.hip).
 #pragma once
 #include "prt_launch.h"
 #include "prt_path.h"
@@ -25,8 +31,20 @@ __device__ __noinline__ V3 sample_sky_call(const float* sky, int32_t w, int32_t 
   return sample_sky(S, D);
 }
 
-// ---- misses of P(iter) (:159): sky radiance (or 0) into ne, before k_shade2 replaces the ray.  EXT: a ray
-// that reaches the area light before any geometry ends there (ne = its MIS-weighted radiance, hit = miss).
+// ---- a segment that misses (:159): the sky radiance (or 0) ends the path, into ne of record e.  rd: the ray's
+// direction where the caller keeps it (a register, or the item's entry of rd, then loaded only under kSkybox)
+__device__ __forceinline__ void shade_miss(const SceneDev& S, const WaveBufs& B, uint32_t fl, size_t e,
+                                           const float4& rd) {
+  V3 L = v3(0.0f, 0.0f, 0.0f);
+  if (fl & kSkybox) {
+    const float4 d = rd;
+    L = sample_sky_call(S.sky, S.skyw, S.skyh, v3(d.x, d.y, d.z));
+  }
+  B.ne[e] = make_float4(L.x, L.y, L.z, 0.0f);
+}
+
+// ---- misses of P(iter) in a pass of their own (extensions, debug modes), before k_shade2 replaces the ray.  EXT: a
+// ray that reaches the area light before any geometry ends there (ne = its MIS-weighted radiance, hit = miss).
 template <bool EXT>
 __device__ __forceinline__ void miss_item(const SceneDev& S, const TraceArgs& A, const WaveBufs& B, uint32_t item) {
   float4 hh = B.hit[item];
@@ -46,12 +64,7 @@ __device__ __forceinline__ void miss_item(const SceneDev& S, const TraceArgs& A,
     }
   }
   if (hh.x < kFar) return;
-  V3 L = v3(0.0f, 0.0f, 0.0f);
-  if (A.flags & kSkybox) {
-    const float4 d = B.rd[item];
-    L = sample_sky_call(S.sky, S.skyw, S.skyh, v3(d.x, d.y, d.z));
-  }
-  B.ne[item] = make_float4(L.x, L.y, L.z, 0.0f);
+  shade_miss(S, B, A.flags, item, B.rd[item]);
 }
 template <bool EXT>
 __global__ void __launch_bounds__(kBlock) k_miss2(SceneDev S, TraceArgs A, WaveBufs B, uint32_t iter) {
@@ -97,8 +110,8 @@ __device__ __forceinline__ bool diel_next(const WaveBufs& B, uint32_t item, uint
   return true;
 }
 
-// ---- the light-visibility record (WaveBufs::lvis; header comment).  An entry is 8 bytes, byte l for light l
-// (x: point lights 0-3, y: kLightDir, kLightSpot): 0 unknown, 1 occluded, 2 unoccluded.  Ray k of an item of
+// ---- the light-visibility record (WaveBufs::lvis; prt_wave2.hip's header comment).  An entry is 8 bytes, byte l for
+// light l (x: point lights 0-3, y: kLightDir, kLightSpot): 0 unknown, 1 occluded, 2 unoccluded.  Ray k of an item of
 // `kind` goes to light k (kind 0) or to the kind's one light (k = 0).
 static_assert(kBlock <= 256, "block_append_skip packs two counts of up to 4 x kBlock into one word");
 // the bytes of this kind's lights, ray k's in byte k -> ask: bit 8k set where ray k's answer is unknown (it is
@@ -137,6 +150,114 @@ __device__ __forceinline__ void queue_live(uint32_t* shq, uint32_t s0, int kind,
     if (live & (1u << k)) shq[s0 + (uint32_t)__popc(live & ((1u << k) - 1u))] = ((l0 + k) << 29) | (4u * vi + k);
 }
 
+// ---- a segment that hits: hit attributes, NEE set-up, BRDF sample -> the segment's record and the item's next ray.
+//   e          the segment's record (hp / ne / nb / nk / vis): the item, or path x n + item in the merged pipeline
+//   ti         its entry of the throughput planes T (EXT: of dro / drd too, which lie alike)
+//   ro, rd     the ray, where the caller keeps it: a register, or the item's entries of the ray buffers -- read once
+//              on entry, before the next ray overwrites them
+//   hh         its hit; kind, nr: the light class drawn for it (nee_kind) and that class's number of shadow rays, > 0
+//   q          what the light-visibility record says about the segment's rays (Asked, below)
+//   shq        the block's part of the shadow queue
+// Returns a ShadedHit.
+// Asked: cached = the record answers for this segment (iteration 0 of a kPrimReuse pass, path 1): shade_hit queues the
+// rays of `ask` (lvis_split; bit 8k = ray k) itself, in compact slots from s0 on, and the visibility word starts as
+// vis0.  Not cached (the default): the rest is 0 and the rays to queue come back in ShadedHit::live
+struct Asked {
+  bool cached = false;
+  uint32_t ask = 0, vis0 = 0, s0 = 0;
+};
+struct ShadedHit {
+  uint32_t rinfo;  // the segment's rinfo bits: status << 16 (kStNeeEnd or kStNeeCont) and kRiEmissive
+  uint32_t live;   // (not cached) the light-class shadow rays to queue behind the NEE block (queue_live), bit k = ray k
+  bool area_ray;   // (EXT) the area light's shadow ray is stored in ao / ad / na, for the caller to queue
+  // the path goes on: ro / rd / info of the item hold the next ray
+  __device__ bool cont() const { return ((rinfo >> 16) & 3u) == kStNeeCont; }
+};
+template <bool EXT>
+__device__ __forceinline__ ShadedHit shade_hit(const SceneDev& S, const TraceArgs& A, const WaveBufs& B, uint32_t item,
+                                               size_t e, size_t ti, const float4& ro, const float4& rd, float4 hh,
+                                               int kind, uint32_t nr, uint32_t info, uint32_t& seed, Asked q,
+                                               uint32_t* shq) {
+  const bool cached = q.cached;
+  const uint32_t ask = q.ask, vis0 = q.vis0, s0 = q.s0;
+  uint32_t live = 0;
+  bool area_ray = false;
+  const uint32_t fl = A.flags;
+  const uint32_t depth = info & 0xFFu, path = (info >> 8) & 1u;
+  const float4 o = ro, d = rd;
+  const V3 D = v3(d.x, d.y, d.z);
+  const uint32_t pk = __float_as_uint(hh.w);
+  const V3 I = v3(o.x, o.y, o.z) + hh.x * D;                                                 // tiny_bvh.h:586
+  const V3 V = -D;
+  const HitAttr ha = hit_attributes(S, hit_inst(S, pk), hit_prim(S, pk), hh.y, hh.z, (fl & kNormalMap) != 0);
+  float4 nk;
+  const V3 brdf = nee_lights(S, fl, kind, I, V, ha.N, ha.m, seed, nk, [&](int k, uint32_t light) {
+    if (cached && (ask & (1u << (8 * k))))  // compact slots: the asked rays below k come first
+      shq[s0 + (uint32_t)__popc(ask & ((1u << (8 * k)) - 1u))] = (light << 29) | (4u * (uint32_t)e + (uint32_t)k);
+  });
+  // dead rays: counted, not queued; their visibility bytes keep the "occluded" 0 stored below
+  if (!cached) live = B.dead ? nee_live(S, fl, kind, nk, brdf, B.dead > 1u) : (1u << nr) - 1u;
+  // a shadow ray is queued as (light, visibility index) with the segment's hit point I stored once: the traversal
+  // kernel rebuilds it (shadow_of, the only reader: a segment that queues no light-class ray needs none)
+  if (cached || live) B.hp[e] = make_float4(I.x, I.y, I.z, 0.0f);
+  uint32_t emissive = 0;
+  const V3 em = v3(0.0f, 0.0f, 0.0f) + v3(1.0f, 1.0f, 1.0f) * ha.m.emis;                    // :196
+  if (em.x != 0.0f || em.y != 0.0f || em.z != 0.0f) {  // otherwise em is +0 and the resolve rebuilds it
+    B.ne[e] = make_float4(em.x, em.y, em.z, 0.0f);
+    emissive = kRiEmissive;
+  }
+  B.nb[e] = make_float4(brdf.x, brdf.y, brdf.z, 0.0f);
+  B.nk[e] = nk;
+  B.vis[e] = vis0;
+  uint32_t status = kStNeeEnd;
+  if constexpr (EXT) {
+    // area-light sample (2 draws after the light-class NEE draws) at lit, non-delta, non-dielectric hits
+    reinterpret_cast<uint8_t*>(B.vis)[4 * (size_t)B.n + item] = 0;
+    if (S.area && (fl & kLighted) && ha.kind != kMatDielectric && !delta_lobe(ha.m)) {
+      const float xi1 = random_float(seed), xi2 = random_float(seed);
+      Ray sr;
+      float tmax;
+      V3 fa;
+      if (area_nee(area_light(S), I, ha.N, V, ha.m, xi1, xi2, sr, tmax, fa)) {
+        area_ray = true;
+        B.ao[item] = make_float4(sr.O.x, sr.O.y, sr.O.z, tmax);
+        B.ad[item] = make_float4(sr.D.x, sr.D.y, sr.D.z, 0.0f);
+        B.na[item] = make_float4(fa.x, fa.y, fa.z, 0.0f);
+      }
+    }
+  }
+  if ((int)depth != A.bounces - 1) {                                                         // :329
+    if (EXT && ha.kind == kMatDielectric) {                                                  // :331-372
+      const Dielectric dl = dielectric_split(I, D, ha.N);
+      B.dro[ti] = make_float4(dl.refr.O.x, dl.refr.O.y, dl.refr.O.z, dl.fresnel);
+      B.drd[ti] = make_float4(dl.refr.D.x, dl.refr.D.y, dl.refr.D.z, 0.0f);
+      B.T[ti] = make_float4(0.0f, 0.0f, 0.0f, kFar);  // w: the continuation is not BRDF-sampled
+      const uint32_t bit = 1u << depth, keep = ~(0x01010101u << depth);
+      B.dst[item] = (B.dst[item] & keep) | bit | (dl.has_refr ? 0u : (bit << 24));
+      status = kStNeeCont;
+      B.ro[item] = make_float4(dl.refl.O.x, dl.refl.O.y, dl.refl.O.z, 0.0f);
+      B.rd[item] = make_float4(dl.refl.D.x, dl.refl.D.y, dl.refl.D.z, 0.0f);
+      B.info[item] = (depth + 1u) | (path << 8);
+    } else {
+      V3 dir, thr;
+      float bp = 2.0f;
+      if (sample_bounce(ha.m, V, ha.N, seed, dir, thr, EXT ? &bp : nullptr)) {               // :376-399
+        status = kStNeeCont;
+        float pdf = 0.0f;
+        if constexpr (EXT)  // MIS density of the sampled direction (kFar: delta lobe or no light sampling)
+          pdf = (bp > 1.0f || !S.area || !(fl & kLighted)) ? kFar : brdf_pdf(ha.m, ha.N, V, dir, bp);
+        B.T[ti] = make_float4(thr.x, thr.y, thr.z, pdf);
+        const Ray nr2 = make_ray(I + dir * kEpsilon, dir);                                   // :404
+        B.ro[item] = make_float4(nr2.O.x, nr2.O.y, nr2.O.z, 0.0f);
+        B.rd[item] = make_float4(nr2.D.x, nr2.D.y, nr2.D.z, 0.0f);
+        B.info[item] = (depth + 1u) | (path << 8);
+      }
+    }
+  }
+  B.seed[item] = seed;
+  return {(status << 16) | emissive, live, area_ray};
+}
+
 // ---- shading of P(iter): NEE set-up -> S(iter), BRDF sample or path-2 start -> P(iter + 1)
 // k_shade2's parameter list as the kernarg segment holds it (explicit arguments in order, each at its natural
 // alignment, as C lays out these members)
@@ -148,20 +269,161 @@ struct Shade2Args {
   uint32_t iter;
 };
 typedef const __attribute__((address_space(4))) Shade2Args* Shade2ArgsPtr;
-// EXT (area light, dielectrics): held to 3 waves/SIMD (168 VGPRs, no spills; unbounded it took 175 and ran 2
-// waves: C5 frame 135.7 -> 132.4 ms).  The plain form runs 4 waves at its natural 125 VGPRs (forcing 5 spilled
-// and was 2 % slower).
+// The body of k_shade2<EXT, I0> (below) and k_shade2d<I0> (prt_defer.hip), whose parameter lists are the same
+// (Shade2Args): the chunk loop, its prefetch and its queue appends around shade_miss / shade_hit.
+// EXT (area light, dielectrics): the misses are shaded by k_miss2 / k_resmiss2.
 // I0 (plain form): iteration 0 of a pass with pmode kPrimReuse and a light-visibility record (B.lvis), an
 // instantiation of its own so that the shading of every other launch carries nothing for it
 // DEFER (plain form): a pass with a deferred resolve (prt_defer.hip k_shade2d / k_resolve_pass).  The host hands the
 // launch the record plane of its iteration in rinfo / ne / nb / nk / vis / T, so the one index that differs is the
 // throughput's: the plane holds one entry per item, not one per depth.
-// The body (prt_shade2_body.inc) is shared by k_shade2 (below) and k_shade2d, whose parameter lists are the same
-// (Shade2Args)
+template <bool EXT, bool I0, bool DEFER>
+__device__ __forceinline__ void shade2_body(const SceneDev& S, const TraceArgs& A, const TileMap& M, const WaveBufs& B,
+                                            uint32_t iter) {
+  static_assert(!(EXT && I0), "the light-visibility record belongs to the plain pipelines");
+  static_assert(!(EXT && DEFER), "the deferred resolve belongs to the plain pipeline");
+  const Shade2ArgsPtr args = (Shade2ArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
+  // fail the call if the Shade2Args layout does not match this compiler's, or the block is not kBlock threads.  The
+  // block-size test also makes blockDim.x a constant for the appends below: read anew inside the chunk loop (a vector
+  // load of the dispatch's group size) it made the I0 forms wait for their prefetch loads, 2 % of the launch
+  if (args->iter != iter || args->B.n != B.n || blockDim.x != kBlock) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(S.diag + 1, 1u);
+    return;
+  }
+  __shared__ uint32_t pref[kNSub + 1];
+  __shared__ uint32_t sm[8];
+  const uint32_t* q = (iter & 1) ? B.q1 : B.q0;
+  uint32_t* qn = (iter & 1) ? B.q0 : B.q1;
+  const uint32_t sub = blockIdx.x % kNSub;
+  uint32_t* shcnt = qcounter(B.ctr, iter, 1, sub);
+  uint32_t* ncnt = qcounter(B.ctr, iter + 1, 0, sub);
+  uint32_t* shq = B.shq + (size_t)sub * B.scap;
+  const uint32_t total = load_prefix(B.ctr, iter, 0, pref);
+  const uint32_t fl = A.flags;
+  // software pipeline over the grid-stride chunks: the next chunk's item, info, hit and seed are loaded while this
+  // chunk's item is shaded
+  uint32_t item_n = 0, info_n = 0, seed_n = 0;
+  float4 hh_n = make_float4(kFar, 0.0f, 0.0f, 0.0f);
+  float4 ro_n = make_float4(0.0f, 0.0f, 0.0f, 0.0f), rd_n = ro_n;  // (plain form: the ray too)
+  uint2 lv_n = make_uint2(0u, 0u);                                 // (I0: the entry's light-visibility bytes)
+  auto prefetch = [&](uint32_t cc) {
+    const uint32_t gg = cc * kBlock + threadIdx.x;
+    if (gg < total) {
+      item_n = q[map_slot(pref, gg, B.qcap)];
+      info_n = B.info[item_n];
+      // iteration 0 with primary-hit reuse (plain form only): the hit of the pixel's fixed path-1 primary ray
+      hh_n = (!EXT && iter == 0 && B.pmode != kPrimTrace) ? B.phit[(B.base + item_n) % B.pitems] : B.hit[item_n];
+      if constexpr (I0) lv_n = B.lvis[(B.base + item_n) % B.pitems];
+      seed_n = B.seed[item_n];
+      if (!EXT) { ro_n = B.ro[item_n]; rd_n = B.rd[item_n]; }
+    }
+  };
+  prefetch(blockIdx.x);
+  for (uint32_t c = blockIdx.x; c * kBlock < total; c += gridDim.x) {
+    const float4 ro_c = ro_n, rd_c = rd_n;
+    // The scene and buffer descriptors are read from the kernarg segment inside each chunk (scalar loads, scalar
+    // cache) instead of being held in SGPRs across the loop: their ~90 live words spilled to VGPR lanes (378
+    // v_readlane in the loop) when hoisted.  The empty asm hides the pointer's loop invariance.
+    Shade2ArgsPtr ka = args;
+    asm volatile("" : "+s"(ka));
+    const SceneDev& Sc = *(const SceneDev*)&ka->S;
+    const WaveBufs& Bc = *(const WaveBufs*)&ka->B;
+    const uint32_t g = c * kBlock + threadIdx.x;
+    uint32_t item = 0, info = 0, seed = 0, nr = 0;
+    Asked q;  // (I0) the rays to queue, the visibility word's initial value, their slots
+    q.cached = I0;
+    int kind = 0;
+    float4 hh = make_float4(kFar, 0.0f, 0.0f, 0.0f);
+    const bool active = g < total;
+    if (active) {
+      item = item_n; info = info_n; hh = hh_n;
+      const uint32_t sd = seed_n;
+      const uint2 lv = lv_n;
+      if ((info & 0x1FFu) == 0) Bc.s1[item].w = hh.x;                                        // r1.hit.t
+      if (!EXT && hh.x >= kFar) shade_miss(Sc, Bc, fl, item, rd_c);
+      if (hh.x < kFar) {
+        seed = sd;
+        kind = nee_kind(fl, seed);                                                           // :198-214
+        nr = (uint32_t)nee_rays(kind);
+        if constexpr (I0) lvis_split(lv, kind, q.ask, q.vis0);
+      }
+    }
+    prefetch(c + gridDim.x);
+    // the block's shadow-ray slots, one atomic (I0: of the rays whose answer is not known yet; the known ones are
+    // counted, not queued).  Every other form appends behind the NEE block, once it knows which rays are live
+    if constexpr (I0)
+      q.s0 = block_append_skip(shcnt, (uint32_t)__popc(q.ask), qcounter(B.ctr, B.lslot, 1, sub), lvis_total(S),
+                               nr - (uint32_t)__popc(q.ask), sm);
+    const uint32_t depth = info & 0xFFu, path = (info >> 8) & 1u;
+    ShadedHit h = {kStMiss << 16, 0u, false};
+    if (nr)
+      h = shade_hit<EXT>(Sc, A, Bc, item, item, DEFER ? (size_t)item : (size_t)depth * Bc.n + item,
+                         EXT ? Bc.ro[item] : ro_c, EXT ? Bc.rd[item] : rd_c, hh, kind, nr, info, seed, q, shq);
+    if constexpr (!I0) {  // only the mask lived across the NEE block: the live rays' slots, the dead ones counted
+      const uint32_t nl = (uint32_t)__popc(h.live);
+      const uint32_t s0 = block_append_skip(shcnt, nl, qcounter(B.ctr, B.lslot, 1, sub), dead_total(S), nr - nl, sm);
+      queue_live(shq, s0, kind, h.live, item);
+    }
+    if constexpr (EXT) {  // the area-light shadow rays of the block, one more append
+      const uint32_t a0 = block_append(shcnt, h.area_ray ? 1u : 0u, sm);
+      if (h.area_ray) shq[a0] = (kLightArea << 29) | item;
+    }
+    bool next = h.cont();
+    if (active) {
+      if (!next) {
+        if (EXT && Sc.has_diel) next = diel_next(Bc, item, depth, path);
+        if (!next) next = start_path2(Sc, A, M, Bc, item, path);
+      }
+      Bc.rinfo[item] = depth | (path << 8) | h.rinfo | ((uint32_t)kind << 20) | (next ? kRiQueued : 0u) |
+                       (EXT ? 0u : kResFresh) | ((I0 && q.ask) ? kRiLearn : 0u);
+    }
+    const uint32_t slot = block_append(ncnt, next ? 1u : 0u, sm);
+    if (next) qn[sub * Bc.qcap + slot] = item;
+  }
+}
+// EXT: held to 3 waves/SIMD (168 VGPRs, no spills; unbounded it took 175 and ran 2 waves: C5 frame 135.7 ->
+// 132.4 ms).  The plain form runs 4 waves at its natural 125 VGPRs (forcing 5 spilled and was 2 % slower).
 template <bool EXT, bool I0 = false>
 __global__ void __launch_bounds__(kBlock, EXT ? 3 : (I0 ? 4 : 1)) k_shade2(SceneDev S, TraceArgs A, TileMap M, WaveBufs B, uint32_t iter) {
-  constexpr bool DEFER = false;
-#include "prt_shade2_body.inc"
+  shade2_body<EXT, I0, false>(S, A, M, B, iter);
+}
+
+// ---- the resolve of one segment.  The four visibility bytes of a segment's light-class rays (1 = unoccluded,
+// written by k_trace2) -> bit k = ray k
+__device__ __forceinline__ uint32_t vis_mask(uint32_t vw) {
+  return ((vw & 0xFFu) ? 1u : 0u) | ((vw & 0xFF00u) ? 2u : 0u) | ((vw & 0xFF0000u) ? 4u : 0u) |
+         ((vw & 0xFF000000u) ? 8u : 0u);
+}
+// one segment's value from its record e (ri = its rinfo): ne (a miss's or a debug mode's end value, or a hit's
+// emissive term, stored only where kRiEmissive) through nee_resolve.  (resolve_item keeps a copy: prt_wave2.hip)
+__device__ __forceinline__ V3 resolve_segment(const SceneDev& S, const WaveBufs& B, size_t e, uint32_t ri, uint32_t fl) {
+  const uint32_t status = (ri >> 16) & 3u, kind = (ri >> 20) & 3u;
+  const bool nee = status == kStNeeEnd || status == kStNeeCont;
+  const float4 ne = (!nee || (ri & kRiEmissive)) ? B.ne[e] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  V3 L = v3(ne.x, ne.y, ne.z);
+  if (nee) {
+    const float4 nb = B.nb[e], nk = B.nk[e];
+    L = nee_resolve(S, (int)kind, vis_mask(B.vis[e]), L, v3(nb.x, nb.y, nb.z), nk, fl);
+  }
+  return L;
+}
+
+// ---- the end of a path.  A pixel's value from its two paths' radiances (a is not used without AA)
+__device__ __forceinline__ V3 pixel_value(V3 a, V3 b, uint32_t fl) {
+  V3 res = (fl & kAA) ? 0.5f * (a + b) : b;                                                  // :65
+  if (fl & kGamma) res = v3(sqrtf(res.x), sqrtf(res.y), sqrtf(res.z));                      // :73-79
+  return res;
+}
+// a path of `item` ended with radiance L: path 1 under AA keeps it in s1 (path 2 follows); otherwise the frame write
+__device__ __forceinline__ void finish_path(const WaveBufs& B, uint32_t item, uint32_t path, V3 L, uint32_t fl,
+                                            float4* __restrict__ out) {
+  const float4 s1 = B.s1[item];
+  if (path == 0 && (fl & kAA)) {
+    B.s1[item] = make_float4(L.x, L.y, L.z, s1.w);
+  } else {
+    const V3 res = pixel_value(v3(s1.x, s1.y, s1.z), L, fl);
+    out[item] = make_float4(res.x, res.y, res.z, s1.w);
+  }
 }
 
 }  // namespace prt

@@ -24,6 +24,11 @@
 //                    sample or path-2 start -> P(i+1)
 // Which instantiation each stage of launch i is, for each of the five pipelines, is wave_schedule (prt_plan.h); which
 // pipeline a call takes is plan_render there.  launch_wave2_iter below only launches what they name.
+// What the pipelines compute per path segment is stated once, in prt_shade2.h: every shading kernel (k_shade2 and
+// k_shade2d through shade2_body, both passes of k_shade2m) shades a segment with shade_miss / shade_hit, and every
+// resolve ends a path with pixel_value.  The kernels differ in their chunk loops, prefetches and queue appends, and in
+// the record index, throughput index and ray they hand those functions.  A segment's resolve stands twice, the one
+// exception: resolve_segment for k_resolve_pass, and written out in resolve_item below, for speed (reason there).
 //
 // Hazards (all kernels on one stream): P(i+1) reuses P(i-1)'s buffer after the resolve (i) read it;
 // S(i) reuses S(i-1)'s buffer after k_trace2(i) read it; the resolve (i) reads ne/nb/nk/vis/R/T of an item for
@@ -308,12 +313,13 @@ __global__ void __launch_bounds__(64, WAVES) k_trace2(SceneDev S, WaveBufs B, ui
 }
 
 }  // namespace prt
-#include "prt_shade2.h"  // k_miss2, k_shade2 and their helpers
+#include "prt_shade2.h"  // k_miss2, k_shade2; the shading and the resolve of one segment, the end of a path
 namespace prt {
 
-// ---- merged pipeline (B.merge: AA, render mode 0, no extensions).  Shading of P(iter) as k_shade2<false>, each
-// path's records (hit point, NEE record, status, (result, throughput) stack) in its own slot (slot = path, at
-// slot * n + item), and where path 1 ends its item shades path 2's first segment at once, from the primary hit
+// ---- merged pipeline (B.merge: AA, render mode 0, no extensions).  Shading of P(iter) by k_shade2<false>'s
+// shade_miss / shade_hit, each path's records (hit point, NEE record, status, (result, throughput) stack) in its own
+// slot (slot = path, at slot * n + item), and where path 1 ends its item shades path 2's first segment at once (pass
+// 1: the same two functions on slot 1, with the ray from ro2 / rd2), from the primary hit
 // k_trace2(0) traced next to path 1's: the RNG stream continues from path 1's last draw exactly as if path 2's
 // primary ray had been traced after path 1 ended, so the result is the same bit for bit and
 // a frame needs one wavefront iteration (a traversal, a shading and a resolve launch) fewer.
@@ -322,7 +328,8 @@ namespace prt {
 template <bool I0>
 __global__ void __launch_bounds__(kBlock, I0 ? 4 : 1) k_shade2m(SceneDev S, TraceArgs A, TileMap M, WaveBufs B, uint32_t iter) {
   const Shade2ArgsPtr args = (Shade2ArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
-  if (args->iter != iter || args->B.n != B.n) {  // the Shade2Args layout does not match this compiler's: fail
+  // the Shade2Args layout does not match this compiler's, or the block is not kBlock threads (shade2_body): fail
+  if (args->iter != iter || args->B.n != B.n || blockDim.x != kBlock) {
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(S.diag + 1, 1u);
     return;
   }
@@ -353,7 +360,7 @@ __global__ void __launch_bounds__(kBlock, I0 ? 4 : 1) k_shade2m(SceneDev S, Trac
   };
   prefetch(blockIdx.x);
   for (uint32_t c = blockIdx.x; c * kBlock < total; c += gridDim.x) {
-    Shade2ArgsPtr ka = args;  // descriptors from the kernarg segment per chunk (k_shade2)
+    Shade2ArgsPtr ka = args;  // descriptors from the kernarg segment per chunk (shade2_body)
     asm volatile("" : "+s"(ka));
     const SceneDev& Sc = *(const SceneDev*)&ka->S;
     const WaveBufs& Bc = *(const WaveBufs*)&ka->B;
@@ -375,76 +382,36 @@ __global__ void __launch_bounds__(kBlock, I0 ? 4 : 1) k_shade2m(SceneDev S, Trac
       const float4* rdp = pass ? Bc.rd2 : Bc.rd;
       int kind = 0;
       uint32_t nr = 0;
-      uint32_t ask = 0, vis0 = 0;  // (I0, pass 0) the rays to queue, bit 8k = ray k; the visibility word's start
-      const bool cached = I0 && pass == 0;
+      Asked q;  // (I0, pass 0) the rays to queue, the visibility word's start, their slots
+      q.cached = I0 && pass == 0;
       if (act) {
         if ((info & 0x1FFu) == 0) Bc.s1[item].w = hh.x;                                     // r1.hit.t
-        if (hh.x >= kFar) {  // a miss (:159): the sky radiance (or 0) ends the path
-          V3 L = v3(0.0f, 0.0f, 0.0f);
-          if (fl & kSkybox) {
-            const float4 d = rdp[item];
-            L = sample_sky_call(Sc.sky, Sc.skyw, Sc.skyh, v3(d.x, d.y, d.z));
-          }
-          Bc.ne[sn] = make_float4(L.x, L.y, L.z, 0.0f);
+        if (hh.x >= kFar) {
+          shade_miss(Sc, Bc, fl, sn, rdp[item]);
         } else {
           kind = nee_kind(fl, seed);                                                        // :198-214
           nr = (uint32_t)nee_rays(kind);
-          if (cached) lvis_split(lv, kind, ask, vis0);
+          if (q.cached) lvis_split(lv, kind, q.ask, q.vis0);
         }
       }
-      // the block's shadow-ray slots, one atomic per pass (I0, pass 0: of the rays not known yet, k_shade2; else
-      // behind the NEE block, of the live rays)
-      uint32_t s0 = 0, live = 0;
-      if (cached)
-        s0 = block_append_skip(shcnt, (uint32_t)__popc(ask), qcounter(B.ctr, B.lslot, 1, sub), lvis_total(S),
-                               nr - (uint32_t)__popc(ask), sm);
-      uint32_t status = kStMiss, emissive = 0;
-      if (nr) {
-        const float4 o = rop[item], d = rdp[item];
-        const V3 D = v3(d.x, d.y, d.z);
-        const uint32_t pk = __float_as_uint(hh.w);
-        const V3 I = v3(o.x, o.y, o.z) + hh.x * D;                                           // tiny_bvh.h:586
-        const V3 V = -D;
-        const HitAttr ha = hit_attributes(Sc, hit_inst(Sc, pk), hit_prim(Sc, pk), hh.y, hh.z, (fl & kNormalMap) != 0);
-        float4 nk;
-        const V3 brdf = nee_lights(Sc, fl, kind, I, V, ha.N, ha.m, seed, nk, [&](int k, uint32_t light) {
-          if (cached && (ask & (1u << (8 * k))))
-            shq[s0 + (uint32_t)__popc(ask & ((1u << (8 * k)) - 1u))] = (light << 29) | (4u * (uint32_t)sn + (uint32_t)k);
-        });
-        if (!cached) live = Bc.dead ? nee_live(Sc, fl, kind, nk, brdf, Bc.dead > 1u) : (1u << nr) - 1u;  // (k_shade2)
-        if (cached || live) Bc.hp[sn] = make_float4(I.x, I.y, I.z, 0.0f);
-        const V3 e = v3(0.0f, 0.0f, 0.0f) + v3(1.0f, 1.0f, 1.0f) * ha.m.emis;                // :196
-        if (e.x != 0.0f || e.y != 0.0f || e.z != 0.0f) {
-          Bc.ne[sn] = make_float4(e.x, e.y, e.z, 0.0f);
-          emissive = kRiEmissive;
-        }
-        Bc.nb[sn] = make_float4(brdf.x, brdf.y, brdf.z, 0.0f);
-        Bc.nk[sn] = nk;
-        Bc.vis[sn] = vis0;
-        status = kStNeeEnd;
-        if ((int)depth != A.bounces - 1) {                                                   // :329
-          V3 dir, thr;
-          if (sample_bounce(ha.m, V, ha.N, seed, dir, thr)) {                               // :376-399
-            status = kStNeeCont;
-            Bc.T[((size_t)path * levels + depth) * Bc.n + item] = make_float4(thr.x, thr.y, thr.z, 0.0f);
-            const Ray nr2 = make_ray(I + dir * kEpsilon, dir);                               // :404
-            Bc.ro[item] = make_float4(nr2.O.x, nr2.O.y, nr2.O.z, 0.0f);
-            Bc.rd[item] = make_float4(nr2.D.x, nr2.D.y, nr2.D.z, 0.0f);
-            Bc.info[item] = (depth + 1u) | (path << 8);
-            next = true;
-          }
-        }
-        Bc.seed[item] = seed;
-      }
-      if (!cached) {  // the live rays' slots; the dead ones counted (k_shade2)
-        const uint32_t nl = (uint32_t)__popc(live);
-        s0 = block_append_skip(shcnt, nl, qcounter(B.ctr, B.lslot, 1, sub), dead_total(S), nr - nl, sm);
-        queue_live(shq, s0, kind, live, (uint32_t)sn);
+      // the block's shadow-ray slots, one atomic per pass (I0, pass 0: of the rays not known yet; else behind the NEE
+      // block, of the live rays), as shade2_body's
+      if (q.cached)
+        q.s0 = block_append_skip(shcnt, (uint32_t)__popc(q.ask), qcounter(B.ctr, B.lslot, 1, sub), lvis_total(S),
+                                 nr - (uint32_t)__popc(q.ask), sm);
+      ShadedHit h = {kStMiss << 16, 0u, false};
+      if (nr)
+        h = shade_hit<false>(Sc, A, Bc, item, sn, ((size_t)path * levels + depth) * Bc.n + item, rop[item], rdp[item],
+                             hh, kind, nr, info, seed, q, shq);
+      if (h.cont()) next = true;
+      if (!q.cached) {  // the live rays' slots; the dead ones counted
+        const uint32_t nl = (uint32_t)__popc(h.live);
+        const uint32_t s0 = block_append_skip(shcnt, nl, qcounter(B.ctr, B.lslot, 1, sub), dead_total(S), nr - nl, sm);
+        queue_live(shq, s0, kind, h.live, (uint32_t)sn);
       }
       if (act) {
-        Bc.rinfo[sn] = depth | (path << 8) | (status << 16) | ((uint32_t)kind << 20) | emissive | kRiFresh |
-                       (ask ? kRiLearn : 0u);
-        need2 = pass == 0 && path == 0 && status != kStNeeCont && (fl & kAA);
+        Bc.rinfo[sn] = depth | (path << 8) | h.rinfo | ((uint32_t)kind << 20) | kRiFresh | (q.ask ? kRiLearn : 0u);
+        need2 = pass == 0 && path == 0 && !h.cont() && (fl & kAA);
       }
     }
     const uint32_t slot = block_append(ncnt, next ? 1u : 0u, sm);
@@ -485,22 +452,27 @@ __global__ void __launch_bounds__(kBlock) k_shade2_debug(SceneDev S, TraceArgs A
   }
 }
 
-// ---- NEE resolve of P(iter) (after k_trace2(iter + 1) traced S(iter)), stack, path end, frame write
+// ---- NEE resolve of P(iter) (after k_trace2(iter + 1) traced S(iter)), stack, path end, frame write.
+// ri: the rinfo of the segment's record e, a segment of `path`; sb: the first level of that path's (result, throughput)
+// stack in R / T.  Plain and extensions pipelines: e = item, sb = 0; merged: e = path x n + item, sb = path x levels.
+// path is bit 8 of ri; it is an argument all the same so that k_res2md's two calls, which know it, hand in a constant
+// and each keeps only its side of the path end (taken from ri there, k_res2md<false> ran 3 us of 36 slower)
 template <bool EXT>
 __device__ __forceinline__ void resolve_item(const SceneDev& S, const TraceArgs& A, const WaveBufs& B, uint32_t item,
-                                             uint32_t ri, float4* __restrict__ out) {
+                                             uint32_t path, uint32_t ri, size_t e, uint32_t sb,
+                                             float4* __restrict__ out) {
   const uint32_t fl = A.flags;
-  const uint32_t depth = ri & 0xFFu, path = (ri >> 8) & 1u, status = (ri >> 16) & 3u, kind = (ri >> 20) & 3u;
-  // ne: the end value (miss, debug mode) or a hit's emissive term, stored only when nonzero (kRiEmissive)
+  const uint32_t depth = ri & 0xFFu, status = (ri >> 16) & 3u;
+  // resolve_segment's expressions (prt_shade2.h) written out, the exception to "one resolve": the extensions' term and
+  // the stack store sit inside the NEE branch, and built from resolve_segment or from halves of it k_res2md<false> ran
+  // 6 % and k_res2d 2 % slower than this form (profiles/shade_resolve_ab.txt)
+  const uint32_t kind = (ri >> 20) & 3u;
   const bool nee = status == kStNeeEnd || status == kStNeeCont;
-  const float4 ne = (!nee || (ri & kRiEmissive)) ? B.ne[item] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  const float4 ne = (!nee || (ri & kRiEmissive)) ? B.ne[e] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   V3 L = v3(ne.x, ne.y, ne.z);
   if (nee) {
-    const float4 nb = B.nb[item], nk = B.nk[item];
-    const uint32_t vw = B.vis[item];
-    const uint32_t vis = ((vw & 0xFFu) ? 1u : 0u) | ((vw & 0xFF00u) ? 2u : 0u) | ((vw & 0xFF0000u) ? 4u : 0u) |
-                         ((vw & 0xFF000000u) ? 8u : 0u);
-    V3 result = nee_resolve(S, (int)kind, vis, L, v3(nb.x, nb.y, nb.z), nk, fl);
+    const float4 nb = B.nb[e], nk = B.nk[e];
+    V3 result = nee_resolve(S, (int)kind, vis_mask(B.vis[e]), L, v3(nb.x, nb.y, nb.z), nk, fl);
     if constexpr (EXT) {
       if (reinterpret_cast<const uint8_t*>(B.vis)[4 * (size_t)B.n + item]) {  // area light unoccluded
         const float4 a = B.na[item];
@@ -508,7 +480,7 @@ __device__ __forceinline__ void resolve_item(const SceneDev& S, const TraceArgs&
       }
     }
     if (status == kStNeeCont) {  // the path goes on: result joins the stack
-      B.R[(size_t)depth * B.n + item] = make_float4(result.x, result.y, result.z, 0.0f);
+      B.R[(size_t)(sb + depth) * B.n + item] = make_float4(result.x, result.y, result.z, 0.0f);
       return;
     }
     L = result;
@@ -519,43 +491,37 @@ __device__ __forceinline__ void resolve_item(const SceneDev& S, const TraceArgs&
     uint32_t ds = S.has_diel ? B.dst[item] : 0u;
     bool parked = false;
     for (int k = (int)depth - 1; k >= 0; k--) {
-      const size_t e = (size_t)k * B.n + item;
+      const size_t ek = (size_t)(sb + (uint32_t)k) * B.n + item;
       const uint32_t bit = 1u << k;
       if (ds & bit) {
-        const float F = B.dro[e].w;
+        const float F = B.dro[ek].w;
         if (ds & (bit << 24)) {
           L = dielectric_combine(F, L, v3(0.0f, 0.0f, 0.0f));
         } else if (!(ds & (bit << 16))) {
-          B.T[e] = make_float4(L.x, L.y, L.z, kFar);
+          B.T[ek] = make_float4(L.x, L.y, L.z, kFar);
           ds |= bit << 16;
           parked = true;
           break;
         } else {
-          const float4 Lr = B.T[e];
+          const float4 Lr = B.T[ek];
           L = dielectric_combine(F, v3(Lr.x, Lr.y, Lr.z), L);
         }
         ds &= ~(0x01010101u << k);
         continue;
       }
-      const float4 Rk = B.R[e], Tk = B.T[e];
+      const float4 Rk = B.R[ek], Tk = B.T[ek];
       L = v3(Rk.x, Rk.y, Rk.z) + L * v3(Tk.x, Tk.y, Tk.z);
     }
     if (S.has_diel) B.dst[item] = ds;
     if (parked) return;
   } else {
     for (int k = (int)depth - 1; k >= 0; k--) {                                            // result + Trace(..) * throughput
-      const float4 Rk = B.R[(size_t)k * B.n + item], Tk = B.T[(size_t)k * B.n + item];
+      const size_t ek = (size_t)(sb + (uint32_t)k) * B.n + item;
+      const float4 Rk = B.R[ek], Tk = B.T[ek];
       L = v3(Rk.x, Rk.y, Rk.z) + L * v3(Tk.x, Tk.y, Tk.z);
     }
   }
-  const float4 s1 = B.s1[item];
-  if (path == 0 && (fl & kAA)) {  // path 2 was queued by k_shade2; keep path 1's radiance
-    B.s1[item] = make_float4(L.x, L.y, L.z, s1.w);
-  } else {
-    V3 res = (fl & kAA) ? 0.5f * (v3(s1.x, s1.y, s1.z) + L) : L;                           // :65
-    if (fl & kGamma) res = v3(sqrtf(res.x), sqrtf(res.y), sqrtf(res.z));                  // :73-79
-    out[item] = make_float4(res.x, res.y, res.z, s1.w);
-  }
+  finish_path(B, item, path, L, fl, out);
 }
 // ---- resolve of P(iter - 1) and the misses of P(iter) in one pass over P(iter - 1): P(iter) is the subset
 // k_shade2(iter - 1) queued (rinfo bit kRiQueued), so each of its items is visited once, resolved first (it
@@ -583,7 +549,7 @@ __global__ void __launch_bounds__(kBlock) k_resmiss2(SceneDev S, TraceArgs A, Wa
     const uint32_t item = item_n, ri = ri_n;
     prefetch(c + gridDim.x);
     if (g >= total) continue;
-    resolve_item<EXT>(S, A, B, item, ri, out);
+    resolve_item<EXT>(S, A, B, item, (ri >> 8) & 1u, ri, item, 0u, out);
     if (misses && iter < iters && (ri & kRiQueued)) miss_item<EXT>(S, A, B, item);
   }
 }
@@ -601,7 +567,7 @@ __global__ void __launch_bounds__(kBlock) k_res2d(SceneDev S, TraceArgs A, WaveB
     const uint32_t ri = ri_n;
     if (item + stride < B.n) ri_n = B.rinfo[item + stride];
     if (!(ri & kRiFresh)) continue;
-    resolve_item<false>(S, A, B, item, ri, out);
+    resolve_item<false>(S, A, B, item, (ri >> 8) & 1u, ri, item, 0u, out);
     if constexpr (LEARN) {
       if (ri & kRiLearn) lvis_learn(B, item, ri);
     }
@@ -609,44 +575,10 @@ __global__ void __launch_bounds__(kBlock) k_res2d(SceneDev S, TraceArgs A, WaveB
   }
 }
 
-// ---- merged pipeline: the resolve of P(iter - 1) per record slot (path 1's, then path 2's), as resolve_item<false>
-__device__ __forceinline__ void resolve_slot(const SceneDev& S, const TraceArgs& A, const WaveBufs& B, uint32_t item,
-                                             uint32_t path, uint32_t ri, float4* __restrict__ out) {
-  const uint32_t fl = A.flags;
-  const uint32_t levels = (uint32_t)max(1, A.bounces - 1);
-  const size_t sn = (size_t)path * B.n + item;
-  const uint32_t depth = ri & 0xFFu, status = (ri >> 16) & 3u, kind = (ri >> 20) & 3u;
-  const bool nee = status == kStNeeEnd || status == kStNeeCont;
-  const float4 ne = (!nee || (ri & kRiEmissive)) ? B.ne[sn] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  V3 L = v3(ne.x, ne.y, ne.z);
-  if (nee) {
-    const float4 nb = B.nb[sn], nk = B.nk[sn];
-    const uint32_t vw = B.vis[sn];
-    const uint32_t vis = ((vw & 0xFFu) ? 1u : 0u) | ((vw & 0xFF00u) ? 2u : 0u) | ((vw & 0xFF0000u) ? 4u : 0u) |
-                         ((vw & 0xFF000000u) ? 8u : 0u);
-    const V3 result = nee_resolve(S, (int)kind, vis, L, v3(nb.x, nb.y, nb.z), nk, fl);
-    if (status == kStNeeCont) {  // the path goes on: result joins its stack
-      B.R[((size_t)path * levels + depth) * B.n + item] = make_float4(result.x, result.y, result.z, 0.0f);
-      return;
-    }
-    L = result;
-  }
-  for (int k = (int)depth - 1; k >= 0; k--) {                                              // result + Trace(..) * throughput
-    const size_t e = ((size_t)path * levels + (uint32_t)k) * B.n + item;
-    const float4 Rk = B.R[e], Tk = B.T[e];
-    L = v3(Rk.x, Rk.y, Rk.z) + L * v3(Tk.x, Tk.y, Tk.z);
-  }
-  const float4 s1 = B.s1[item];
-  if (path == 0 && (fl & kAA)) {  // path 2 follows (shaded in the same iteration); keep path 1's radiance
-    B.s1[item] = make_float4(L.x, L.y, L.z, s1.w);
-  } else {
-    V3 res = (fl & kAA) ? 0.5f * (v3(s1.x, s1.y, s1.z) + L) : L;                           // :65
-    if (fl & kGamma) res = v3(sqrtf(res.x), sqrtf(res.y), sqrtf(res.z));                  // :73-79
-    out[item] = make_float4(res.x, res.y, res.z, s1.w);
-  }
-}
+// ---- merged pipeline: the resolve of P(iter - 1) per record slot (path 1's, then path 2's), each with its own stack
 template <bool LEARN>  // (as k_res2d's; slot 0 is path 1)
 __global__ void __launch_bounds__(kBlock) k_res2md(SceneDev S, TraceArgs A, WaveBufs B, float4* __restrict__ out) {
+  const uint32_t levels = (uint32_t)max(1, A.bounces - 1);  // of each path's (result, throughput) stack
   const uint32_t stride = gridDim.x * kBlock;
   uint32_t item = blockIdx.x * kBlock + threadIdx.x;
   uint32_t r0_n = 0, r1_n = 0;
@@ -655,14 +587,14 @@ __global__ void __launch_bounds__(kBlock) k_res2md(SceneDev S, TraceArgs A, Wave
     const uint32_t r0 = r0_n, r1 = r1_n;
     if (item + stride < B.n) { r0_n = B.rinfo[item + stride]; r1_n = B.rinfo[B.n + item + stride]; }
     if (r0 & kRiFresh) {
-      resolve_slot(S, A, B, item, 0u, r0, out);
+      resolve_item<false>(S, A, B, item, 0u, r0, item, 0u, out);
       if constexpr (LEARN) {
         if (r0 & kRiLearn) lvis_learn(B, item, r0);
       }
       B.rinfo[item] = r0 & ~(kRiFresh | kRiLearn);
     }
     if (r1 & kRiFresh) {
-      resolve_slot(S, A, B, item, 1u, r1, out);
+      resolve_item<false>(S, A, B, item, 1u, r1, (size_t)B.n + item, levels, out);
       B.rinfo[B.n + item] = r1 & ~kRiFresh;
     }
   }
