@@ -75,7 +75,9 @@ typedef struct {
     const uint32_t* pixels;
 } prt_texture;
 
-/* one Model (Core/Model.h:36-44).  T = tri_count, V = vertex_count. */
+/* one Model (Core/Model.h:36-44).  T = tri_count, V = vertex_count.
+ * fixed_uvs must be >= 0: values >= 1 wrap around the texture, and a negative UV indexes outside the texture as
+ * in the reference (Core/Scene.cpp:82-83,163-164) and is undefined. */
 typedef struct {
     int32_t tri_count;
     int32_t vertex_count;

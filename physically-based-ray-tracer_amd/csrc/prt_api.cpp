@@ -774,9 +774,10 @@ int prt_set_meshes(prt_ctx* c, const prt_mesh* m_in, int32_t n) {
     const TexDev& A = c->tex_host[M.albedo_tex];
     for (int k = 1; k < 4; k++) {
       if (tx[k] >= ntex) return fail(PRT_ERR_INVALID_ARGUMENT, "texture id out of range");
-      // every map is indexed with the albedo dimensions (Scene.cpp:79-85,160-165)
-      if (tx[k] >= 0 && (c->tex_host[tx[k]].w * (int64_t)c->tex_host[tx[k]].h < (int64_t)A.w * A.h ||
-                         c->tex_host[tx[k]].w < A.w))
+      // every map is read at the flat texel iu + iv * albedo width, iu and iv taken with the albedo dimensions
+      // (Scene.cpp:79-85,160-165): the map needs that many texels, whatever its own width (a narrower, taller map
+      // renders in the reference and must here)
+      if (tx[k] >= 0 && c->tex_host[tx[k]].w * (int64_t)c->tex_host[tx[k]].h < (int64_t)A.w * A.h)
         return fail(PRT_ERR_INVALID_ARGUMENT, "texture smaller than the albedo map (indexed with albedo dims)");
     }
     for (int64_t k = 0; k < 3 * (int64_t)M.tri_count; k++)
