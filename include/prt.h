@@ -210,6 +210,17 @@ int prt_set_meshes(prt_ctx* ctx, const prt_mesh* meshes, int32_t count);
  * stale.  No scene: PRT_ERR_NOT_READY.  A NaN coordinate is ignored by the boxes, as the builders ignore it. */
 #define PRT_IN_DEVICE (1u << 0)
 int prt_update_mesh(prt_ctx* ctx, int32_t mesh_index, const prt_mesh* mesh, uint32_t in_flags);
+/* (additive in ABI 10; DESIGN.md "Deforming meshes") Keeps mesh mesh_index's present object-space corner positions as
+ * its previous positions: nine floats per primitive in prim order, vertices[indices[3p + k]] for k = 0..2, as the last
+ * prt_set_meshes or prt_update_mesh of the mesh left them.  prt_render_aov_deform measures against them.  A copy from
+ * device memory to device memory by a kernel on the context stream: frames and updates enqueued before the call are
+ * what it sees.  The storage (36 bytes per primitive) is per mesh, allocated at that mesh's first snapshot and kept: a
+ * mesh never snapshotted costs nothing, the first snapshot of a mesh allocates and waits for the context stream once,
+ * every later one neither allocates nor waits on the host.  A second snapshot overwrites the first; prt_update_mesh
+ * never touches a snapshot; prt_set_meshes discards all of them.  On a local group or RCCL context it applies to every
+ * member, as the setters do.  The call joins the frames in flight.
+ * NULL context or an index out of range: PRT_ERR_INVALID_ARGUMENT.  No meshes: PRT_ERR_NOT_READY. */
+int prt_snapshot_mesh(prt_ctx* ctx, int32_t mesh_index);
 /* transforms: 16*count floats, row-major BLASInstance::transform; mesh_index: count.  Above 64 instances the rays
  * walk an instance BVH, rebuilt for every call as the reference's per-frame BVH::Build (a host SAH build): on the
  * calling thread when the instance count changes, otherwise on the context's worker thread, the context stream
@@ -499,7 +510,8 @@ int prt_instance_motion(const float* transforms, const float* prev_transforms, i
  * Image pointers all host, or all device with PRT_OUT_DEVICE (then the call does not wait on the host).  What
  * prt_reproject says about frames in flight, sharded contexts, side effects and Panini holds here too.
  * Not tracked: lighting that changes because an object moved (its shadow on a static surface lags by up to
- * max_history frames; prt_reproject_moments' clamp_k below shortens that), deforming meshes. */
+ * max_history frames; prt_reproject_moments' clamp_k below shortens that).  Deforming meshes are followed by
+ * prt_reproject_deform below. */
 int prt_reproject_motion(prt_ctx* ctx, const prt_reproject_params* params, int32_t width, int32_t height,
                          const prt_camera* camera, const float* color_rgba, const float* normal_depth,
                          const uint32_t* instance, const prt_camera* prev_camera, const float* history_rgba,
@@ -579,6 +591,54 @@ int prt_denoise_variance_defaults(prt_denoise_variance_params* out);
 int prt_denoise_variance(prt_ctx* ctx, const prt_denoise_variance_params* params, int32_t width, int32_t height,
                          const float* color_rgba, const float* moments, const float* albedo_rgba,
                          const float* normal_depth, float* out_rgba, float* out_variance, uint32_t* out_rgb8,
+                         uint32_t out_flags);
+
+/* ---- deforming meshes in the temporal reprojection (ABI 10, additive; DESIGN.md "Deforming meshes") ----
+ * The frame loop: prt_update_mesh -> prt_set_instances -> prt_render -> prt_render_aov_deform -> prt_instance_motion ->
+ * prt_reproject_deform -> prt_denoise_variance -> prt_snapshot_mesh.  The snapshot at the end makes this frame's
+ * geometry the next frame's previous geometry; a mesh that is not updated in the following frame then has offset 0
+ * (INTEGRATION.md). */
+
+/* (ABI 10, additive) prt_render_aov_ids with one more output, from the same single primary-hit pass:
+ *   offset  float4 W*H.  For a hit pixel whose instance's mesh has a snapshot (prt_snapshot_mesh), with (prim, u, v)
+ *           as prt_trace_primary reports them, c_k the mesh's current corners of prim and q_k the snapshotted ones
+ *           (k = 0..2): d_k = q_k - c_k per component, w0 = (1 - u) - v,
+ *           offset.xyz = (w0 * d_0 + u * d_1) + v * d_2 per component, offset.w = 1; every operation a correctly
+ *           rounded f32, no contraction.  A miss, or a mesh without a snapshot: (0, 0, 0, 0).
+ * The offset is in the mesh's object space: the displacement from where the surface point is now to where it was at
+ * the snapshot.  A snapshot that equals the current positions gives exactly (0, 0, 0, 1).
+ * Everything else is prt_render_aov_ids' contract: every output may be NULL, host pointers unless PRT_OUT_DEVICE,
+ * PRT_OUT_TIMED times the whole pass including the offset (ms[0] of prt_denoise_timings), no effect on the
+ * accumulation or the ray totals; the other three outputs equal prt_render_aov_ids' bit for bit. */
+int prt_render_aov_deform(prt_ctx* ctx, int32_t width, int32_t height, uint32_t flags, float* albedo_rgba,
+                          float* normal_depth, uint32_t* instance, float* offset, uint32_t out_flags);
+
+/* (ABI 10, additive) prt_reproject_moments whose carried-back point follows the deformation.  The definition is
+ * prt_reproject_moments' word for word with one change.  With i = instance[p], A = motion[i], L the upper-left 3x3 of
+ * prev_transforms[i], delta = offset[p].xyz and X the pixel's world-space hit, row r of the point carried back is
+ *   offset[p].w != 0:  X'_r = row4(A_r, X) + ((L_r.x * delta.x + L_r.y * delta.y) + L_r.z * delta.z)
+ *   offset[p].w == 0:  X'_r = row4(A_r, X), as in prt_reproject_moments
+ * where row4(A_r, X) = ((A_r.x * X.x + A_r.y * X.y) + A_r.z * X.z) + A_r.w.  Since A = T_prev * inverse(T_cur), X' is
+ * T_prev applied to the object-space point at its previous position.  Everything after X' is unchanged: the
+ * projection, the previous depth, the taps, the id test, the moments, the clamp, the spatial variance and the
+ * start-over rules.
+ * The normal used for the tap test stays unit(A3x3 * N): previous normals are not kept, so a deformation that turns
+ * the surface by more than acos(normal_min) between two frames loses that pixel's history.
+ *   offset           this view's prt_render_aov_deform buffer: an image pointer under the same host / device rule as
+ *                    the others; must not be an output
+ *   prev_transforms  always a host array: count row-major 4x4 matrices, the previous frame's prt_set_instances input
+ *                    (what prt_instance_motion took as prev_transforms).  Only the upper-left 3x3 is read.  Copied
+ *                    before the call returns and uploaded in the context stream's order with motion.
+ * offset and prev_transforms are both NULL or both given, and given only together with a history; anything else is
+ * PRT_ERR_INVALID_ARGUMENT.  Every other rule is prt_reproject_moments'.  With both NULL every output equals
+ * prt_reproject_moments' bit for bit; so it does with an offset buffer whose xyz are all +0 and finite transforms
+ * (a + 0 = a for every a but -0). */
+int prt_reproject_deform(prt_ctx* ctx, const prt_temporal_params* params, int32_t width, int32_t height,
+                         const prt_camera* camera, const float* color_rgba, const float* normal_depth,
+                         const uint32_t* instance, const prt_camera* prev_camera, const float* history_rgba,
+                         const float* history_normal_depth, const uint32_t* history_instance, const float* motion,
+                         int32_t count, const float* history_moments, const float* offset,
+                         const float* prev_transforms, float* out_rgba, float* out_moments, uint32_t* out_rgb8,
                          uint32_t out_flags);
 
 /* ---- shading-function probe (ABI 10): the device's own BRDF functions (the ones the shading kernels inline) on

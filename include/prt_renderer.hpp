@@ -8,6 +8,7 @@
 // reference's assimp / JSON loading, Core/Scene.cpp:10-28,279-340, stays where it is), physics and UI
 // are not part of this header, and errors surface as prt::Error exceptions instead of crashes.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <stdexcept>
@@ -444,9 +445,13 @@ class Renderer {
   // 0x00RRGGBB pixels, history the unfiltered reprojection output.  The unfiltered output and its moments are the
   // next call's history (the filtered image is not fed back).  A changed instance count, ResetTemporal() or a
   // preceding TickTemporal() / TickTemporalMotion() starts a new history.
+  // deform = true follows the models given to TrackModel() as ModelChanged() deforms them: the AOVs come from
+  // prt_render_aov_deform, the pass is prt_reproject_deform with the kept previous transforms, and every tracked model
+  // is snapshotted again after the pass (prt_snapshot_mesh).
   void TickTemporalVariance(std::vector<float>& filtered, std::vector<uint32_t>& screen8, std::vector<float>& history,
                             const prt_temporal_params& params = TemporalDefaults(),
-                            const prt_denoise_variance_params& filter = DenoiseVarianceDefaults()) {
+                            const prt_denoise_variance_params& filter = DenoiseVarianceDefaults(),
+                            bool deform = false) {
     if (isPostProcessed)
       throw Error(PRT_ERR_INVALID_ARGUMENT,
                   "temporal reprojection is defined for the plane projection only (isPostProcessed is set)");
@@ -457,9 +462,14 @@ class Renderer {
     Tick();
     const size_t n = (size_t)width_ * height_;
     std::vector<float> albedo(4 * n, 0.0f), normal_depth(4 * n, 0.0f), out(4 * n, 0.0f), mom(4 * n, 0.0f), xf;
+    std::vector<float> offset(deform ? 4 * n : 0, 0.0f);
     std::vector<uint32_t> ids(n, 0u);
-    check(prt_render_aov_ids(ctx_, width_, height_, NORMALMAPPED ? PRT_FLAG_NORMALMAP : 0u, albedo.data(),
-                             normal_depth.data(), ids.data(), 0u));
+    if (deform)
+      check(prt_render_aov_deform(ctx_, width_, height_, NORMALMAPPED ? PRT_FLAG_NORMALMAP : 0u, albedo.data(),
+                                  normal_depth.data(), ids.data(), offset.data(), 0u));
+    else
+      check(prt_render_aov_ids(ctx_, width_, height_, NORMALMAPPED ? PRT_FLAG_NORMALMAP : 0u, albedo.data(),
+                               normal_depth.data(), ids.data(), 0u));
     for (const GameObject& g : scene.gameobjects) xf.insert(xf.end(), g.transform.begin(), g.transform.end());
     const int32_t count = (int32_t)scene.gameobjects.size();
     if (hist_.empty() || hist_ids_.empty() || hist_mom_.empty() || hist_xf_.size() != xf.size() || count == 0) {
@@ -469,14 +479,22 @@ class Renderer {
     } else {
       std::vector<float> motion(12 * (size_t)count);
       check(prt_instance_motion(xf.data(), hist_xf_.data(), count, motion.data()));
-      check(prt_reproject_moments(ctx_, &params, width_, height_, &cam, accumulator.data(), normal_depth.data(),
-                                  ids.data(), &hist_cam_, hist_.data(), hist_nd_.data(), hist_ids_.data(),
-                                  motion.data(), count, hist_mom_.data(), out.data(), mom.data(), nullptr, 0u));
+      if (deform)
+        check(prt_reproject_deform(ctx_, &params, width_, height_, &cam, accumulator.data(), normal_depth.data(),
+                                   ids.data(), &hist_cam_, hist_.data(), hist_nd_.data(), hist_ids_.data(),
+                                   motion.data(), count, hist_mom_.data(), offset.data(), hist_xf_.data(), out.data(),
+                                   mom.data(), nullptr, 0u));
+      else
+        check(prt_reproject_moments(ctx_, &params, width_, height_, &cam, accumulator.data(), normal_depth.data(),
+                                    ids.data(), &hist_cam_, hist_.data(), hist_nd_.data(), hist_ids_.data(),
+                                    motion.data(), count, hist_mom_.data(), out.data(), mom.data(), nullptr, 0u));
     }
     filtered.assign(4 * n, 0.0f);
     screen8.assign(n, 0u);
     check(prt_denoise_variance(ctx_, &filter, width_, height_, out.data(), mom.data(), albedo.data(),
                                normal_depth.data(), filtered.data(), nullptr, screen8.data(), 0u));
+    if (deform)
+      for (int32_t index : tracked_) check(prt_snapshot_mesh(ctx_, index));
     hist_ = out;
     hist_nd_.swap(normal_depth);
     hist_ids_.swap(ids);
@@ -484,6 +502,12 @@ class Renderer {
     hist_mom_.swap(mom);
     hist_cam_ = cam;
     history.swap(out);
+  }
+  // scene.models[index] deforms (ModelChanged every frame): its present positions are snapshotted now
+  // (prt_snapshot_mesh), and TickTemporalVariance(deform = true) renews the snapshot after every pass
+  void TrackModel(int32_t index) {
+    check(prt_snapshot_mesh(ctx_, index));
+    if (std::find(tracked_.begin(), tracked_.end(), index) == tracked_.end()) tracked_.push_back(index);
   }
   // the next TickTemporal() / TickTemporalMotion() / TickTemporalVariance() starts a new history
   void ResetTemporal() {
@@ -512,6 +536,7 @@ class Renderer {
   std::vector<uint32_t> hist_ids_;     // TickTemporalMotion's: the previous instance ids (empty: no such history)
   std::vector<float> hist_xf_;         // ... and the previous instance transforms (16 floats each)
   std::vector<float> hist_mom_;        // TickTemporalVariance's: the previous moments (empty: no such history)
+  std::vector<int32_t> tracked_;       // TrackModel's models
 };
 
 }  // namespace prt

@@ -19,6 +19,7 @@
 #include "bvh_gpu.h"
 #include "prt_blas_refit.h"
 #include "prt_ctx.h"
+#include "prt_deform.h"
 #include "prt_denoise.h"
 #include "prt_motion.h"
 
@@ -892,6 +893,9 @@ int prt_set_meshes(prt_ctx* c, const prt_mesh* m_in, int32_t n) {
   c->mesh_host = mh;
   c->mesh_info = info;
   c->max_depth = maxd;
+  c->snap.clear();  // the snapshots of the previous meshes (prt_snapshot_mesh): nothing queued reads them (drain)
+  c->snap_host.clear();
+  c->snap_tab.release();
   c->inst_dirty = true;
   c->tlas_dirty = true;
   c->scene_epoch++;  // new geometry and BLASes (and prim bits of the hit word): kept primary hits are stale
@@ -987,6 +991,35 @@ int prt_update_mesh(prt_ctx* c, int32_t mi, const prt_mesh* M, uint32_t in_flags
   c->scene_epoch++;  // new geometry: kept primary hits and light visibility are stale
   if (bad) return fail(PRT_ERR_INVALID_ARGUMENT, "mesh update: an index in device memory is out of range (vertex 0 was read in its place)");
   PRT_FOR_MEMBERS(prt_update_mesh(m, mi, M, in_flags));
+  return PRT_OK;
+}
+
+int prt_snapshot_mesh(prt_ctx* c, int32_t mi) {
+  if (!c) return fail(PRT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  if (c->mesh_host.empty()) return fail(PRT_ERR_NOT_READY, "no meshes: call prt_set_meshes");
+  if (mi < 0 || (size_t)mi >= c->mesh_host.size()) return fail(PRT_ERR_INVALID_ARGUMENT, "mesh index out of range");
+  PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t nmesh = c->mesh_host.size();
+  const MeshDev& md = c->mesh_host[mi];
+  if (c->snap.size() != nmesh) {  // the context's first snapshot of these meshes: the table, no snapshot anywhere
+    c->snap.clear();
+    c->snap.resize(nmesh);
+    c->snap_host.assign(nmesh, nullptr);
+    HIP_TRY(c->snap_tab.ensure(nmesh * sizeof(const float*)));
+    HIP_TRY(hipMemsetAsync(c->snap_tab.p, 0, nmesh * sizeof(const float*), c->stream));
+  }
+  if (!c->snap[mi].p) {  // the mesh's first snapshot: its storage, and its entry in the table (the one host wait)
+    HIP_TRY(c->snap[mi].ensure(36 * (size_t)md.tri_count));
+    c->snap_host[mi] = c->snap[mi].as<const float>();
+    const int rc = wait_stream(c, "prt_snapshot_mesh");
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(c->snap_tab.as<const float*>() + mi, &c->snap_host[mi], sizeof(const float*),
+                      hipMemcpyHostToDevice));
+  }
+  HIP_TRY(launch_snapshot_mesh(c->stream, c->stri.as<ShadeTri>() + md.prim_base, md.tri_count,
+                               c->snap[mi].as<float>()));
+  PRT_FOR_MEMBERS(prt_snapshot_mesh(m, mi));
   return PRT_OK;
 }
 
@@ -1280,9 +1313,10 @@ int prt_occluded(prt_ctx* c, int32_t n, const float* O, const float* D, const fl
 
 // ---- first-hit AOVs and the a-trous denoiser (prt_denoise.hip)
 namespace {
-// prt_render_aov / prt_render_aov_ids: one primary-hit pass, then k_aov and / or k_aov_ids over its hits
+// prt_render_aov / prt_render_aov_ids / prt_render_aov_deform: one primary-hit pass, then k_aov, k_aov_ids and / or
+// k_aov_deform over its hits
 int render_aov(prt_ctx* c, int32_t W, int32_t H, uint32_t flags, float* albedo, float* normal_depth,
-               uint32_t* instance, uint32_t out_flags) {
+               uint32_t* instance, float* offset, uint32_t out_flags) {
   if (!c || W <= 0 || H <= 0 || W > 16384 || H > 16384) return fail(PRT_ERR_INVALID_ARGUMENT, "bad AOV arguments");
   PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
   HIP_TRY(hipSetDevice(c->device));
@@ -1291,7 +1325,7 @@ int render_aov(prt_ctx* c, int32_t W, int32_t H, uint32_t flags, float* albedo, 
   if (rc) return rc;
   if (!c->have_camera) return fail(PRT_ERR_NOT_READY, "no camera");
   if (!depth_ok(c)) return fail(PRT_ERR_UNSUPPORTED, "BVH deeper than 64 levels");
-  if (!albedo && !normal_depth && !instance) return PRT_OK;
+  if (!albedo && !normal_depth && !instance && !offset) return PRT_OK;
   const TileMap M = make_tilemap(W, H, 8, 0, 1);
   const size_t n = (size_t)W * H;
   rc = ensure_spill(c, S, (size_t)M.items + 256);
@@ -1302,16 +1336,21 @@ int render_aov(prt_ctx* c, int32_t W, int32_t H, uint32_t flags, float* albedo, 
   float4* a = reinterpret_cast<float4*>(albedo);
   float4* g = reinterpret_cast<float4*>(normal_depth);
   uint32_t* ids = instance;
+  float4* off = reinterpret_cast<float4*>(offset);
   Staging io(c, out_flags);
   PRT_TRY(io.out(c->aov_alb, a, n * sizeof(float4)));
   PRT_TRY(io.out(c->aov_nd, g, n * sizeof(float4)));
   PRT_TRY(io.out(c->aov_ids, ids, n * 4));
+  PRT_TRY(io.out(c->aov_off, off, n * sizeof(float4)));
   LaunchCfg L{c->stream, occ_for(c)};
   if (timed && (rc = dn_event(c, 0))) return rc;
   HIP_TRY(launch_primary_hits(L, S, M, c->aov_hits.as<HitOut>(), c->counters.as<Counters>()));
   if (a || g)
     HIP_TRY(launch_aov(c->stream, S, W, H, (flags & PRT_FLAG_NORMALMAP) != 0, c->aov_hits.as<HitOut>(), a, g));
   if (ids) HIP_TRY(launch_aov_ids(c->stream, W, H, c->aov_hits.as<HitOut>(), ids));
+  if (off)  // (no snapshot since the last prt_set_meshes: no table, every pixel gets zeros)
+    HIP_TRY(launch_aov_deform(c->stream, S, W, H, c->aov_hits.as<HitOut>(),
+                              c->snap.empty() ? nullptr : c->snap_tab.as<const float*>(), off));
   if (timed) {
     if ((rc = dn_event(c, 1))) return rc;
     c->dn_timed_aov = 1;
@@ -1322,11 +1361,15 @@ int render_aov(prt_ctx* c, int32_t W, int32_t H, uint32_t flags, float* albedo, 
 
 int prt_render_aov(prt_ctx* c, int32_t W, int32_t H, uint32_t flags, float* albedo, float* normal_depth,
                    uint32_t out_flags) {
-  return render_aov(c, W, H, flags, albedo, normal_depth, nullptr, out_flags);
+  return render_aov(c, W, H, flags, albedo, normal_depth, nullptr, nullptr, out_flags);
 }
 int prt_render_aov_ids(prt_ctx* c, int32_t W, int32_t H, uint32_t flags, float* albedo, float* normal_depth,
                        uint32_t* instance, uint32_t out_flags) {
-  return render_aov(c, W, H, flags, albedo, normal_depth, instance, out_flags);
+  return render_aov(c, W, H, flags, albedo, normal_depth, instance, nullptr, out_flags);
+}
+int prt_render_aov_deform(prt_ctx* c, int32_t W, int32_t H, uint32_t flags, float* albedo, float* normal_depth,
+                          uint32_t* instance, float* offset, uint32_t out_flags) {
+  return render_aov(c, W, H, flags, albedo, normal_depth, instance, offset, out_flags);
 }
 
 int prt_brdf_probe(prt_ctx* c, int32_t op, int32_t n, const float* in, float* out) {

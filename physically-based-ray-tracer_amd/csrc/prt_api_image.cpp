@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "prt_ctx.h"
+#include "prt_deform.h"
 #include "prt_denoise.h"
 #include "prt_motion.h"
 #include "prt_temporal.h"
@@ -41,7 +42,8 @@ DenoisePass denoise_pass(int32_t W, int32_t H, int32_t normal_power, float sigma
 
 // ---- the three reprojections: prt_reproject is the core, prt_reproject_motion adds the motion group (id images and
 // the instances' motion matrices), prt_reproject_moments adds the moments group on top of that; the pass structs nest
-// the same way (MomentsPass > MotionPass > ReprojectPass)
+// the same way (MomentsPass > MotionPass > ReprojectPass); prt_reproject_deform is the moments level with an offset
+// image and the previous transforms (DeformPass > MomentsPass)
 enum ReprojectLevel { kCore = 0, kMotion = 1, kMoments = 2 };
 
 bool reproject_params_ok(float depth_tol, float normal_min, float max_history) {
@@ -70,20 +72,25 @@ ReprojectPass reproject_pass(int32_t W, int32_t H, float depth_tol, float normal
   return P;
 }
 
-// the motion matrices: copied into a pinned staging buffer now, uploaded in stream order (no host wait)
-int upload_motion(prt_ctx* c, const float* motion, int32_t count) {
-  const size_t mb = 12 * sizeof(float) * (size_t)count;
-  HIP_TRY(c->rp_motion.ensure(mb));
+// the motion matrices, and with prev_xf (count row-major 4 x 4 transforms) their first three rows after them: copied
+// into a pinned staging buffer now, uploaded in stream order (no host wait)
+int upload_motion(prt_ctx* c, const float* motion, const float* prev_xf, int32_t count) {
+  const size_t mb = 12 * sizeof(float) * (size_t)count, all = prev_xf ? 2 * mb : mb;
+  HIP_TRY(c->rp_motion.ensure(all));
   StageSlot* st = nullptr;
-  PRT_TRY(stage_acquire(c, mb, st));
+  PRT_TRY(stage_acquire(c, all, st));
   std::memcpy(st->p, motion, mb);
-  HIP_TRY(hipMemcpyAsync(c->rp_motion.p, st->p, mb, hipMemcpyHostToDevice, c->stream));
+  for (int32_t k = 0; prev_xf && k < count; k++)
+    std::memcpy(static_cast<char*>(st->p) + mb + 48 * (size_t)k, prev_xf + 16 * (size_t)k, 48);
+  HIP_TRY(hipMemcpyAsync(c->rp_motion.p, st->p, all, hipMemcpyHostToDevice, c->stream));
   return stage_release(c, *st, c->stream);
 }
 
 // After an entry point's argument checks: stage the images of the groups this level has, launch its kernel, copy
-// back.  Q holds the caller's pointers (the groups above `level` unset); motion is null without a history.
-int reproject(prt_ctx* c, ReprojectLevel level, MomentsPass Q, const float* motion, uint32_t out_flags) {
+// back.  Q holds the caller's pointers (the groups above `level` unset); motion is null without a history.  offset
+// and prev_xf (prt_reproject_deform: kMoments with a history, both or neither) select k_reproject_deform.
+int reproject(prt_ctx* c, ReprojectLevel level, MomentsPass Q, const float* motion, uint32_t out_flags,
+              const float* offset = nullptr, const float* prev_xf = nullptr) {
   PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
   HIP_TRY(hipSetDevice(c->device));
   MotionPass& M = Q.M;
@@ -99,12 +106,18 @@ int reproject(prt_ctx* c, ReprojectLevel level, MomentsPass Q, const float* moti
     PRT_TRY(io.in(c->rp_ids[1], M.hist_inst, n * 4));
   }
   if (level == kMoments) PRT_TRY(io.in(c->rp_mom[0], Q.hist_mom, bytes));
+  PRT_TRY(io.in(c->rp_off, offset, bytes));
   PRT_TRY(io.out(c->rp_out, R.out, bytes));
   if (level == kMoments) PRT_TRY(io.out(c->rp_mom[1], Q.mom, bytes));
   PRT_TRY(io.out(c->rp_rgb8, R.rgb8, n * 4));
   if (motion) {
-    PRT_TRY(upload_motion(c, motion, M.count));
+    PRT_TRY(upload_motion(c, motion, prev_xf, M.count));
     M.motion = c->rp_motion.as<float4>();
+  }
+  if (offset) {
+    DeformPass D{Q, reinterpret_cast<const float4*>(offset), M.motion + 3 * (size_t)M.count};
+    HIP_TRY(launch_reproject_deform(c->stream, D));
+    return io.finish();
   }
   if (level == kCore) HIP_TRY(launch_reproject(c->stream, R));
   else if (level == kMotion) HIP_TRY(launch_reproject_motion(c->stream, M));
@@ -296,11 +309,13 @@ int prt_temporal_defaults(prt_temporal_params* out) {
   return PRT_OK;
 }
 
-int prt_reproject_moments(prt_ctx* c, const prt_temporal_params* p, int32_t W, int32_t H, const prt_camera* cam,
-                          const float* color, const float* normal_depth, const uint32_t* instance,
-                          const prt_camera* prev_cam, const float* history, const float* history_nd,
-                          const uint32_t* history_inst, const float* motion, int32_t count, const float* history_mom,
-                          float* out_rgba, float* out_mom, uint32_t* out_rgb8, uint32_t out_flags) {
+// prt_reproject_moments, and with offset and prev_xf prt_reproject_deform
+static int reproject_moments(prt_ctx* c, const prt_temporal_params* p, int32_t W, int32_t H, const prt_camera* cam,
+                             const float* color, const float* normal_depth, const uint32_t* instance,
+                             const prt_camera* prev_cam, const float* history, const float* history_nd,
+                             const uint32_t* history_inst, const float* motion, int32_t count,
+                             const float* history_mom, const float* offset, const float* prev_xf, float* out_rgba,
+                             float* out_mom, uint32_t* out_rgb8, uint32_t out_flags) {
   if (!c || !p || !cam || !color || !normal_depth || !instance || !out_mom || (!out_rgba && !out_rgb8) ||
       !size_ok(W, H))
     return fail(PRT_ERR_INVALID_ARGUMENT, "bad reproject arguments");
@@ -312,6 +327,10 @@ int prt_reproject_moments(prt_ctx* c, const prt_temporal_params* p, int32_t W, i
   if (count < 0 || (given != 0 && given != 6) || (given == 0 && history_inst))
     return fail(PRT_ERR_INVALID_ARGUMENT,
                 "prev_camera, history_rgba, history_normal_depth, motion, count > 0 and history_moments go together");
+  if ((offset != nullptr) != (prev_xf != nullptr) || (offset && !given))
+    return fail(PRT_ERR_INVALID_ARGUMENT, "offset and prev_transforms go together, and with a history");
+  if (offset && (static_cast<const void*>(offset) == out_rgba || static_cast<const void*>(offset) == out_mom))
+    return fail(PRT_ERR_INVALID_ARGUMENT, "offset must not be an output");
   if (out_rgba == color)  // the clamp and the spatial estimate read the neighbours of color_rgba
     return fail(PRT_ERR_INVALID_ARGUMENT, "out_rgba must not be color_rgba");
   if (out_rgba && (out_rgba == normal_depth || out_rgba == out_mom ||
@@ -332,7 +351,27 @@ int prt_reproject_moments(prt_ctx* c, const prt_temporal_params* p, int32_t W, i
   Q.mom = reinterpret_cast<float4*>(out_mom);
   Q.clamp_k = p->clamp_k;
   Q.min_temporal = p->min_temporal;
-  return reproject(c, kMoments, Q, motion, out_flags);
+  return reproject(c, kMoments, Q, motion, out_flags, offset, prev_xf);
+}
+
+int prt_reproject_moments(prt_ctx* c, const prt_temporal_params* p, int32_t W, int32_t H, const prt_camera* cam,
+                          const float* color, const float* normal_depth, const uint32_t* instance,
+                          const prt_camera* prev_cam, const float* history, const float* history_nd,
+                          const uint32_t* history_inst, const float* motion, int32_t count, const float* history_mom,
+                          float* out_rgba, float* out_mom, uint32_t* out_rgb8, uint32_t out_flags) {
+  return reproject_moments(c, p, W, H, cam, color, normal_depth, instance, prev_cam, history, history_nd, history_inst,
+                           motion, count, history_mom, nullptr, nullptr, out_rgba, out_mom, out_rgb8, out_flags);
+}
+
+// ---- deforming meshes in the reprojection (prt_deform.hip; prt_snapshot_mesh and prt_render_aov_deform: prt_api.cpp)
+int prt_reproject_deform(prt_ctx* c, const prt_temporal_params* p, int32_t W, int32_t H, const prt_camera* cam,
+                         const float* color, const float* normal_depth, const uint32_t* instance,
+                         const prt_camera* prev_cam, const float* history, const float* history_nd,
+                         const uint32_t* history_inst, const float* motion, int32_t count, const float* history_mom,
+                         const float* offset, const float* prev_transforms, float* out_rgba, float* out_mom,
+                         uint32_t* out_rgb8, uint32_t out_flags) {
+  return reproject_moments(c, p, W, H, cam, color, normal_depth, instance, prev_cam, history, history_nd, history_inst,
+                           motion, count, history_mom, offset, prev_transforms, out_rgba, out_mom, out_rgb8, out_flags);
 }
 
 int prt_denoise_variance_defaults(prt_denoise_variance_params* out) {

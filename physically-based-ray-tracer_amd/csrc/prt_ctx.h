@@ -273,6 +273,15 @@ struct prt_ctx {
   // moments and variance (prt_reproject_moments / prt_denoise_variance): the staging of host moments images (the
   // previous one, the output; the filter's input) and of the filter's variance output
   DevBuf rp_mom[2], dn_mom, dn_var;
+  // deforming meshes (prt_snapshot_mesh / prt_render_aov_deform / prt_reproject_deform): per mesh the snapshot of its
+  // primitives' corners (nine floats each; empty until the mesh's first snapshot), the device table of their
+  // addresses (one per mesh, null = no snapshot; allocated by a context's first snapshot) and its host copy; the
+  // staging of the offset output and of a host offset image.  prt_set_meshes discards the snapshots.  The previous
+  // transforms' rows follow the motion matrices in rp_motion.
+  std::vector<DevBuf> snap;
+  std::vector<const float*> snap_host;
+  DevBuf snap_tab;
+  DevBuf aov_off, rp_off;
 };
 
 namespace prt::host {

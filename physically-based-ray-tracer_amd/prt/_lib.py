@@ -38,6 +38,7 @@ EXPORTS = [
     "prt_render_aov_ids", "prt_instance_motion", "prt_reproject_motion",
     "prt_temporal_defaults", "prt_reproject_moments", "prt_denoise_variance_defaults", "prt_denoise_variance",
     "prt_update_mesh", "prt_read_blas", "prt_read_blas_tris",
+    "prt_snapshot_mesh", "prt_render_aov_deform", "prt_reproject_deform",
 ]
 SHARD_ID_BYTES = 128
 SHARD_NONE, SHARD_RCCL, SHARD_GROUP = 0, 1, 2  # prt_shard_info.transport
@@ -171,6 +172,7 @@ def load():
         "prt_set_textures": ([vp, C.POINTER(Texture), i32], C.c_int),
         "prt_set_meshes": ([vp, C.POINTER(Mesh), i32], C.c_int),
         "prt_update_mesh": ([vp, i32, C.POINTER(Mesh), u32], C.c_int),
+        "prt_snapshot_mesh": ([vp, i32], C.c_int),
         "prt_read_blas": ([vp, i32, vp, C.c_uint64, C.POINTER(C.c_uint64)], C.c_int),
         "prt_read_blas_tris": ([vp, i32, vp, C.c_uint64, C.POINTER(C.c_uint64)], C.c_int),
         "prt_set_instances": ([vp, vp, vp, i32], C.c_int),
@@ -220,6 +222,9 @@ def load():
         "prt_temporal_defaults": ([C.POINTER(TemporalParams)], C.c_int),
         "prt_reproject_moments": ([vp, C.POINTER(TemporalParams), i32, i32, C.POINTER(CameraDesc), vp, vp, vp,
                                    C.POINTER(CameraDesc), vp, vp, vp, vp, i32, vp, vp, vp, vp, u32], C.c_int),
+        "prt_render_aov_deform": ([vp, i32, i32, u32, vp, vp, vp, vp, u32], C.c_int),
+        "prt_reproject_deform": ([vp, C.POINTER(TemporalParams), i32, i32, C.POINTER(CameraDesc), vp, vp, vp,
+                                  C.POINTER(CameraDesc), vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, u32], C.c_int),
         "prt_denoise_variance_defaults": ([C.POINTER(DenoiseVarianceParams)], C.c_int),
         "prt_denoise_variance": ([vp, C.POINTER(DenoiseVarianceParams), i32, i32, vp, vp, vp, vp, vp, vp, vp, u32],
                                  C.c_int),

@@ -359,6 +359,12 @@ class Context:
         m = _lib.Mesh(int(tri_count), int(verts), *ptrs, mesh.albedo, mesh.normal, mesh.metalness, mesh.emission)
         check(self.L.prt_update_mesh(self.h, int(index), C.byref(m), _lib.IN_DEVICE if device else 0))
 
+    def snapshot_mesh(self, index):
+        """prt_snapshot_mesh: mesh `index`'s present corner positions become its previous positions, which
+        render_aov_deform() measures against (a device copy on the context stream; a mesh's first snapshot allocates,
+        later ones neither allocate nor wait)."""
+        check(self.L.prt_snapshot_mesh(self.h, int(index)))
+
     def read_blas(self, index):
         """prt_read_blas: mesh `index`'s Node8 records as a uint8 array [nodes, 80], child_base / tri_base relative to
         the mesh (introspection for tests and tools; waits for the context stream)."""
@@ -602,6 +608,44 @@ class Context:
         check(self.L.prt_denoise_variance(self.h, C.byref(dp), width, height, *map(_ptr, ins + outs), of))
         return tuple(outs)
 
+    # -- deforming meshes in the reprojection (include/prt.h prt_render_aov_deform / prt_reproject_deform)
+    def render_aov_deform(self, width, height, flags=_lib.FLAG_NORMALMAP, device_out=False, albedo=None,
+                          normal_depth=None, instance=None, offset=None, timed=False):
+        """render_aov_ids() with the first hit's object-space displacement to where its surface point was at the
+        mesh's snapshot_mesh() (xyz, w = 1; a miss or a mesh without a snapshot: zeros), from the same primary-hit
+        pass: (albedo[n,4], normal_depth[n,4], instance[n], offset[n,4]).  device_out: the four are raw device
+        pointers (any may be None)."""
+        _, _, outs, of = _images(width * height, device_out, timed,
+                                 outs=((albedo, 4, F32), (normal_depth, 4, F32), (instance, 1, np.uint32),
+                                       (offset, 4, F32)))
+        check(self.L.prt_render_aov_deform(self.h, width, height, flags, *map(_ptr, outs), of))
+        return tuple(outs)
+
+    def reproject_deform(self, color, normal_depth, instance, camera, history=None, history_normal_depth=None,
+                         prev_camera=None, history_instance=None, motion=None, history_moments=None, offset=None,
+                         prev_transforms=None, *, width, height, params=None, device_out=False, out=None, moments=None,
+                         rgb8=None):
+        """reproject_moments() that follows deforming meshes: `offset` is this view's render_aov_deform() buffer and
+        `prev_transforms` the previous frame's instance transforms ([count, 16], always a host array, what
+        instance_motion() took); both None or both given, and given only with a history.  Returns (out[n,4],
+        moments[n,4], rgb8[n])."""
+        tp = params if params is not None else temporal_defaults()
+        cam = _camera_desc(camera)
+        prev = C.byref(_camera_desc(prev_camera)) if prev_camera is not None else None
+        mo = _f32(motion).reshape(-1, 12) if motion is not None else None
+        pxf = _f32(prev_transforms).reshape(-1, 16) if prev_transforms is not None else None
+        if mo is not None and pxf is not None and len(pxf) != len(mo):
+            raise ValueError("reproject_deform: motion and prev_transforms differ in count")
+        (c, g, h, hg, hm, off), (i, hi), (out, moments, rgb8), of = _images(
+            width * height, device_out, False,
+            (color, normal_depth, history, history_normal_depth, history_moments, offset),
+            (instance, history_instance), ((out, 4, F32), (moments, 4, F32), (rgb8, 1, np.uint32)))
+        check(self.L.prt_reproject_deform(
+            self.h, C.byref(tp), width, height, C.byref(cam),
+            *map(_ptr, (c, g, i, prev, h, hg, hi, mo, 0 if mo is None else len(mo), hm, off, pxf, out, moments,
+                        rgb8)), of))
+        return out, moments, rgb8
+
     def intersect(self, O, D, tmax=None):
         O, D = _f32(O), _f32(D)
         n = O.shape[0]
@@ -684,6 +728,7 @@ class Renderer:
         self.last_stats = None
         # TickTemporal's history: (width, height, out, normal_depth, camera[, ids, transforms[, moments]])
         self._temporal = None
+        self._tracked = []  # TrackModel: the models whose snapshot TickTemporalVariance(deform=True) renews
         self.Init()
 
     def Init(self):
@@ -767,16 +812,29 @@ class Renderer:
         self._temporal = (W, H, out, nd, cam, ids, xf)
         return out, rgb8
 
-    def TickTemporalVariance(self, params=None, filter_params=None):
+    def TrackModel(self, index):
+        """Model `index` deforms (UpdateModel every frame): its present positions are snapshotted now
+        (Context.snapshot_mesh) and TickTemporalVariance(deform=True) renews the snapshot after every pass, so each
+        frame's reprojection measures the deformation since the previous frame."""
+        self.ctx.snapshot_mesh(index)
+        if index not in self._tracked:
+            self._tracked.append(index)
+
+    def TickTemporalVariance(self, params=None, filter_params=None, deform=False):
         """TickTemporal(motion=True) with the luminance moments carried along (reproject_moments, `params`:
         temporal_defaults()) and the result filtered by denoise_variance (`filter_params`:
         denoise_variance_defaults()).  Returns (filtered, screen, history): the filtered float4 image, its 0x00RRGGBB
         pixels and the unfiltered reprojection output.  The unfiltered output and its moments are the next call's
         history (the filtered image is not fed back).  A changed image size or instance count, ResetTemporal() or a
-        preceding TickTemporal() starts a new history."""
+        preceding TickTemporal() starts a new history.
+        deform=True follows the models given to TrackModel() as UpdateModel() deforms them: the AOVs come from
+        render_aov_deform, the pass is reproject_deform with the kept previous transforms, and every tracked model is
+        snapshotted again after the pass."""
         if self.isPostProcessed:
             raise ValueError(PANINI_REPROJECT)
         W, H = self.width, self.height
+        if deform:
+            return self._tick_temporal_deform(params, filter_params, W, H)
         self.ctx.set_instances(self.scene.blases)
         self.ctx.set_camera(self.camera)
         self.ctx.reset_accumulation(full=True)
@@ -796,6 +854,30 @@ class Renderer:
                                                      params=params)
         self._temporal = (W, H, out, nd, cam, ids, xf, mom)
         filtered, _, rgb8 = self.ctx.denoise_variance(out, mom, alb, nd, W, H, filter_params, want_variance=False)
+        return filtered, rgb8, out
+
+    def _tick_temporal_deform(self, params, filter_params, W, H):
+        self.ctx.set_instances(self.scene.blases)
+        self.ctx.set_camera(self.camera)
+        self.ctx.reset_accumulation(full=True)
+        self.Tick()
+        alb, nd, ids, off = self.ctx.render_aov_deform(W, H, _lib.FLAG_NORMALMAP if self.NORMALMAPPED else 0)
+        cam = _camera_desc(self.camera)
+        xf = _f32(np.stack([T for _, T in self.scene.blases])).reshape(-1, 16).copy()
+        t = self._temporal
+        if t is not None and (t[:2] != (W, H) or len(t) != 8 or len(t[6]) != len(xf)):
+            t = None
+        if t is None:
+            out, mom, _ = self.ctx.reproject_deform(self.average, nd, ids, cam, width=W, height=H, params=params)
+        else:
+            hist, hist_nd, prev, hist_ids, prev_xf, hist_mom = t[2:]
+            out, mom, _ = self.ctx.reproject_deform(self.average, nd, ids, cam, hist, hist_nd, prev, hist_ids,
+                                                    instance_motion(xf, prev_xf), hist_mom, off, prev_xf, width=W,
+                                                    height=H, params=params)
+        self._temporal = (W, H, out, nd, cam, ids, xf, mom)
+        filtered, _, rgb8 = self.ctx.denoise_variance(out, mom, alb, nd, W, H, filter_params, want_variance=False)
+        for index in self._tracked:
+            self.ctx.snapshot_mesh(index)
         return filtered, rgb8, out
 
     def ResetTemporal(self):
