@@ -221,6 +221,54 @@ int prt_update_mesh(prt_ctx* ctx, int32_t mesh_index, const prt_mesh* mesh, uint
  * member, as the setters do.  The call joins the frames in flight.
  * NULL context or an index out of range: PRT_ERR_INVALID_ARGUMENT.  No meshes: PRT_ERR_NOT_READY. */
 int prt_snapshot_mesh(prt_ctx* ctx, int32_t mesh_index);
+/* Linear-blend skinning inside the boundary (additive in ABI 10; DESIGN.md 8 "Skinning"; the definition, operation by
+ * operation: csrc/prt_skin.h).  prt_set_mesh_skin binds a mesh's bind pose once; prt_skin_mesh takes the frame's joint
+ * matrices, skins the vertices and normals, derives the arrays prt_update_mesh takes and refits the BLAS, all on the
+ * device.  With w the four weights and j the four joints of vertex v, M the row-major 3 x 4 joint matrices (a joint's
+ * world matrix times its inverse bind matrix, in the mesh's object space), every operation one f32 rounding in the
+ * order written:
+ *   B[r][c] = ((w0*M[j0][r][c] + w1*M[j1][r][c]) + w2*M[j2][r][c]) + w3*M[j3][r][c]
+ *   P'_r = ((B[r][0]*P.x + B[r][1]*P.y) + B[r][2]*P.z) + B[r][3]     n_r = (B[r][0]*N.x + B[r][1]*N.y) + B[r][2]*N.z
+ *   N' = n * (1.0f / sqrtf((n.x*n.x + n.y*n.y) + n.z*n.z)), (0, 1, 0) if any component is not finite
+ *   triangles[3p + k] = (P'[i_k], 0), fixed_normals[3p + k] = (N'[i_k], 0), vertices = P' (i_k = indices[3p + k]),
+ *   face_normals[p] = normalize(cross(P'[i_1] - P'[i_0], P'[i_2] - P'[i_0])), (0, 0, 0) if not finite;
+ *   fixed_uvs, the texture ids stay.
+ * The weights are used as given (never renormalised; a weight of 0 still names a joint that must be in range).  The
+ * normal goes through B's 3 x 3 part itself: exact for rotations and uniform scales, approximate otherwise (the choice
+ * prt_reproject_motion makes for its normals).
+ * The contract: after prt_skin_mesh every query, render, AOV, prt_read_blas and prt_read_blas_tris returns, bit for
+ * bit, what the same context returns after prt_update_mesh with the six arrays derived as above, whatever builder
+ * made the tree. */
+typedef struct {
+    int32_t vertex_count, tri_count;   /* must equal the mesh's */
+    int32_t joint_count;               /* 1..65536 */
+    const float*    positions;         /* float3 x V, bind pose */
+    const float*    normals;           /* float3 x V */
+    const int32_t*  indices;           /* int x 3T, the mesh's own */
+    const uint16_t* joints;            /* 4 x V */
+    const float*    weights;           /* 4 x V */
+} prt_skin;
+/* Binds *skin (host arrays) to mesh mesh_index, replacing an earlier binding; skin = NULL removes it.  The counts are
+ * checked against the mesh, every index against vertex_count and every joint against joint_count, on the host:
+ * PRT_ERR_INVALID_ARGUMENT, and nothing changes.  The call joins the frames in flight, waits for the context stream,
+ * may allocate, and uploads into storage the context keeps per mesh.  Resident bytes per bound mesh:
+ * 80 V + 60 T + 48 J (the binding 48 V + 12 T, the matrices 48 J, the scratch of the skinned vertices and fat
+ * triangles 32 V + 48 T), each array rounded up to 256 bytes.  prt_set_meshes discards every binding; prt_update_mesh
+ * leaves them alone.  On a local group or RCCL context it applies to every member.
+ * NULL context or an index out of range: PRT_ERR_INVALID_ARGUMENT.  No meshes: PRT_ERR_NOT_READY. */
+int prt_set_mesh_skin(prt_ctx* ctx, int32_t mesh_index, const prt_skin* skin);
+/* Skins mesh mesh_index with joint_matrices (12 floats per joint, row-major 3 x 4) and refits its BLAS in place.
+ * in_flags = 0: host memory, copied before the call returns and uploaded in the context stream's order.
+ * in_flags = PRT_IN_DEVICE: device memory on the context's device, 16-byte aligned, read in the context stream's
+ * order; on a local group PRT_ERR_UNSUPPORTED.  The matrices are not checked for finiteness: a NaN coordinate is
+ * ignored by the boxes, as in prt_update_mesh.
+ * Ordering, frames in flight and what goes stale are prt_update_mesh's: the call joins the frames in flight and
+ * enqueues on the context stream; kept primary hits and light visibility go stale; the instance boxes and the instance
+ * BVH follow at the next frame.  The call waits on the host once, for the mesh's new root box, after its own kernels;
+ * after the first call on a binding nothing is allocated.
+ * No binding on the mesh: PRT_ERR_NOT_READY.  joint_count different from the binding's, NULL matrices, unknown
+ * flags, a bad index: PRT_ERR_INVALID_ARGUMENT. */
+int prt_skin_mesh(prt_ctx* ctx, int32_t mesh_index, const float* joint_matrices, int32_t joint_count, uint32_t in_flags);
 /* transforms: 16*count floats, row-major BLASInstance::transform; mesh_index: count.  Above 64 instances the rays
  * walk an instance BVH, rebuilt for every call as the reference's per-frame BVH::Build (a host SAH build): on the
  * calling thread when the instance count changes, otherwise on the context's worker thread, the context stream

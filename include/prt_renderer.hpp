@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <array>
 #include <cstdint>
+#include <map>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -42,6 +43,16 @@ struct Model {
   int32_t TriCount() const { return (int32_t)(indices.size() / 3); }
 };
 
+// A model's skin (prt_set_mesh_skin): the bind pose and, per vertex, four joints and four weights; the corner indices
+// are the model's own
+struct Skin {
+  std::vector<float> positions;   // float3 x V, bind pose
+  std::vector<float> normals;     // float3 x V
+  std::vector<uint16_t> joints;   // 4 x V
+  std::vector<float> weights;     // 4 x V
+  int32_t jointCount = 0;
+};
+
 // Surface (template/surface.h:49-94): packed 0x00RRGGBB pixels
 struct Texture {
   int32_t width = 0, height = 0;
@@ -64,6 +75,7 @@ class Scene {
   std::vector<float> skyPixels;     // Camera::skyPixels, float RGB equirect (empty = no sky)
   int32_t skyWidth = 0, skyHeight = 0;
   std::vector<prt_area_light> areaLights;  // Scene::areaLights (Core/AreaLight.h): at most one, sampled with MIS
+  std::map<int32_t, Skin> skins;           // model index -> its skin (SetSkin); Upload binds them again
 
   // everything the hot path reads, copied to HBM (Scene::Init + BuildTLAS, Core/Scene.cpp:10-28,220-223)
   void Upload(prt_ctx* ctx) const {
@@ -92,6 +104,33 @@ class Scene {
     check(prt_set_lights(ctx, &lights));
     check(prt_set_area_lights(ctx, areaLights.empty() ? nullptr : areaLights.data(), (int32_t)areaLights.size()));
     check(prt_set_sky(ctx, skyPixels.empty() ? nullptr : skyPixels.data(), skyWidth, skyHeight));
+    for (const auto& kv : skins) BindSkin(ctx, kv.first, kv.second);  // (prt_set_meshes discarded the bindings)
+  }
+  // models[index] is skinned from now on: the scene keeps `skin` and the device takes it (prt_set_mesh_skin; ctx may
+  // be null before the first Upload, which binds every kept skin).  Renderer::SkinModel then poses the model.
+  void SetSkin(prt_ctx* ctx, int32_t index, Skin skin) {
+    if (ctx) BindSkin(ctx, index, skin);
+    skins[index] = std::move(skin);
+  }
+  void RemoveSkin(prt_ctx* ctx, int32_t index) {
+    if (ctx) check(prt_set_mesh_skin(ctx, index, nullptr));
+    skins.erase(index);
+  }
+  void BindSkin(prt_ctx* ctx, int32_t index, const Skin& k) const {
+    const Model& m = models.at((size_t)index);
+    prt_skin d{};
+    d.vertex_count = (int32_t)(k.positions.size() / 3);
+    d.tri_count = m.TriCount();
+    d.joint_count = k.jointCount;
+    d.positions = k.positions.data();
+    d.normals = k.normals.data();
+    d.indices = m.indices.data();
+    d.joints = k.joints.data();
+    d.weights = k.weights.data();
+    if (k.normals.size() != k.positions.size() || k.joints.size() != 4 * (size_t)d.vertex_count ||
+        k.weights.size() != k.joints.size())
+      throw Error(PRT_ERR_INVALID_ARGUMENT, "Skin: positions, normals, joints and weights differ in vertex count");
+    check(prt_set_mesh_skin(ctx, index, &d));
   }
   // models[index] was deformed in place (same topology): its arrays go to the device and its BLAS is refitted there
   // (prt_update_mesh); the instance boxes and the instance BVH follow at the next frame
@@ -280,6 +319,15 @@ class Renderer {
   // the accumulation restarts in full (the accumulated frames, sample counts and distances show the old geometry)
   void ModelChanged(int32_t index) {
     scene.UpdateModel(ctx_, index);
+    check(prt_reset_accumulation(ctx_, 1));
+  }
+
+  // scene.models[index] is bound to `skin` (Scene::SetSkin); SkinModel(index, matrices, joints) then poses it: joints
+  // row-major 3 x 4 matrices from host memory, skinned and refitted on the device (prt_skin_mesh), and the
+  // accumulation restarts in full as after ModelChanged.  The scene's Model keeps its bind-pose arrays.
+  void SetSkin(int32_t index, Skin skin) { scene.SetSkin(ctx_, index, std::move(skin)); }
+  void SkinModel(int32_t index, const float* matrices, int32_t joints) {
+    check(prt_skin_mesh(ctx_, index, matrices, joints, 0u));
     check(prt_reset_accumulation(ctx_, 1));
   }
 

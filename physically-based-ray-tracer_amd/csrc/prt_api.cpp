@@ -896,6 +896,7 @@ int prt_set_meshes(prt_ctx* c, const prt_mesh* m_in, int32_t n) {
   c->snap.clear();  // the snapshots of the previous meshes (prt_snapshot_mesh): nothing queued reads them (drain)
   c->snap_host.clear();
   c->snap_tab.release();
+  c->skin.clear();  // the skin bindings of the previous meshes (prt_set_mesh_skin), likewise
   c->inst_dirty = true;
   c->tlas_dirty = true;
   c->scene_epoch++;  // new geometry and BLASes (and prim bits of the hit word): kept primary hits are stale
@@ -1020,6 +1021,127 @@ int prt_snapshot_mesh(prt_ctx* c, int32_t mi) {
   HIP_TRY(launch_snapshot_mesh(c->stream, c->stri.as<ShadeTri>() + md.prim_base, md.tri_count,
                                c->snap[mi].as<float>()));
   PRT_FOR_MEMBERS(prt_snapshot_mesh(m, mi));
+  return PRT_OK;
+}
+
+int prt_set_mesh_skin(prt_ctx* c, int32_t mi, const prt_skin* S) {
+  if (!c) return fail(PRT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  if (c->mesh_host.empty()) return fail(PRT_ERR_NOT_READY, "no meshes: call prt_set_meshes");
+  if (mi < 0 || (size_t)mi >= c->mesh_host.size()) return fail(PRT_ERR_INVALID_ARGUMENT, "mesh index out of range");
+  if (S) {  // every check on the host, before anything changes
+    const MeshHost& mh = c->mesh_info[mi];
+    if (S->vertex_count != mh.verts || S->tri_count != mh.tris)
+      return fail(PRT_ERR_INVALID_ARGUMENT, "mesh skin: the vertex and triangle counts must equal the mesh's");
+    if (S->joint_count < 1 || S->joint_count > 65536)
+      return fail(PRT_ERR_INVALID_ARGUMENT, "mesh skin: joint_count must be 1..65536");
+    if (!S->positions || !S->normals || !S->indices || !S->joints || !S->weights)
+      return fail(PRT_ERR_INVALID_ARGUMENT, "mesh skin: missing arrays");
+    for (size_t k = 0; k < 3 * (size_t)S->tri_count; k++)
+      if (S->indices[k] < 0 || S->indices[k] >= S->vertex_count) return fail(PRT_ERR_INVALID_ARGUMENT, "mesh skin: index out of range");
+    for (size_t k = 0; k < 4 * (size_t)S->vertex_count; k++)
+      if ((int32_t)S->joints[k] >= S->joint_count) return fail(PRT_ERR_INVALID_ARGUMENT, "mesh skin: joint out of range");
+  }
+  PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
+  HIP_TRY(hipSetDevice(c->device));
+  // an earlier prt_skin_mesh's kernels may still read the binding this call replaces or removes
+  int rc = wait_stream(c, "prt_set_mesh_skin");
+  if (rc) return rc;
+  if (c->skin.size() != c->mesh_host.size()) {
+    c->skin.clear();
+    c->skin.resize(c->mesh_host.size());
+  }
+  SkinBinding& b = c->skin[mi];
+  b.joints = 0;
+  if (!S) {
+    b = SkinBinding();
+    PRT_FOR_MEMBERS(prt_set_mesh_skin(m, mi, S));
+    return PRT_OK;
+  }
+  const size_t V = (size_t)S->vertex_count, T = (size_t)S->tri_count, J = (size_t)S->joint_count;
+  const void* src[5] = {S->positions, S->normals, S->joints, S->weights, S->indices};
+  const size_t bytes[5] = {12 * V, 12 * V, 8 * V, 16 * V, 12 * T};
+  size_t off[5], at = 0;
+  for (int k = 0; k < 5; k++) {
+    off[k] = at;
+    at += (bytes[k] + 255) & ~size_t(255);
+  }
+  HIP_TRY(b.in.ensure(at));
+  HIP_TRY(b.mats.ensure(48 * J));
+  HIP_TRY(b.work.ensure(32 * V + 48 * T));
+  for (int k = 0; k < 5; k++)
+    if (bytes[k]) HIP_TRY(hipMemcpy(b.in.as<char>() + off[k], src[k], bytes[k], hipMemcpyHostToDevice));
+  SkinDev& d = b.dev;
+  d.positions = reinterpret_cast<const float*>(b.in.as<char>() + off[0]);
+  d.normals = reinterpret_cast<const float*>(b.in.as<char>() + off[1]);
+  d.joints = reinterpret_cast<const uint2*>(b.in.as<char>() + off[2]);
+  d.weights = reinterpret_cast<const float4*>(b.in.as<char>() + off[3]);
+  d.indices = reinterpret_cast<const int32_t*>(b.in.as<char>() + off[4]);
+  d.matrices = b.mats.as<const float4>();
+  d.vpos = b.work.as<float4>();
+  d.vnrm = d.vpos + V;
+  d.triangles = d.vnrm + V;
+  d.vertex_count = S->vertex_count;
+  d.tri_count = S->tri_count;
+  d.joint_count = S->joint_count;
+  b.joints = S->joint_count;
+  PRT_FOR_MEMBERS(prt_set_mesh_skin(m, mi, S));
+  return PRT_OK;
+}
+
+int prt_skin_mesh(prt_ctx* c, int32_t mi, const float* M, int32_t J, uint32_t in_flags) {
+  if (!c) return fail(PRT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  if (in_flags & ~PRT_IN_DEVICE) return fail(PRT_ERR_INVALID_ARGUMENT, "unknown input flags");
+  if (c->mesh_host.empty()) return fail(PRT_ERR_NOT_READY, "no meshes: call prt_set_meshes");
+  if (mi < 0 || (size_t)mi >= c->mesh_host.size()) return fail(PRT_ERR_INVALID_ARGUMENT, "mesh index out of range");
+  const bool dev_in = (in_flags & PRT_IN_DEVICE) != 0;
+  if (dev_in && c->sh_kind == 2) return fail(PRT_ERR_UNSUPPORTED, "device matrices on a local shard group");
+  if (c->skin.size() != c->mesh_host.size() || !c->skin[mi].joints)
+    return fail(PRT_ERR_NOT_READY, "no skin bound to the mesh: call prt_set_mesh_skin");
+  SkinBinding& b = c->skin[mi];
+  if (!M) return fail(PRT_ERR_INVALID_ARGUMENT, "joint_matrices is NULL");
+  if (J != b.joints) return fail(PRT_ERR_INVALID_ARGUMENT, "joint_count differs from the binding's");
+  if (dev_in && (reinterpret_cast<uintptr_t>(M) & 15u))
+    return fail(PRT_ERR_INVALID_ARGUMENT, "device joint matrices must be 16-byte aligned");
+  PRT_JOIN(c);  // frames in flight complete first: they read the geometry this call rewrites in place
+  HIP_TRY(hipSetDevice(c->device));
+  int rc = refit_scratch(c, false);
+  if (rc) return rc;
+  rc = refit_levels(c, mi);
+  if (rc) return rc;
+  const MeshDev& md = c->mesh_host[mi];
+  MeshHost& mh = c->mesh_info[mi];
+  SkinDev d = b.dev;
+  if (dev_in) {
+    d.matrices = reinterpret_cast<const float4*>(M);
+  } else {  // copied into a pinned staging buffer now, uploaded in stream order
+    StageSlot* st = nullptr;
+    PRT_TRY(stage_acquire(c, 48 * (size_t)J, st));
+    std::memcpy(st->p, M, 48 * (size_t)J);
+    HIP_TRY(hipMemcpyAsync(b.mats.p, st->p, 48 * (size_t)J, hipMemcpyHostToDevice, c->stream));
+    PRT_TRY(stage_release(c, *st, c->stream));
+  }
+  HIP_TRY(launch_skin_mesh(c->stream, d, c->stri.as<ShadeTri>() + md.prim_base));
+  // the refit over the scratch's fat triangles: the record pass without its ShadeTri kernel (tri_count 0: k_skin_prims
+  // wrote those words), then the node levels
+  RefitResult* res = c->rf_res.as<RefitResult>();
+  RefitMeshDev r = {};
+  r.triangles = reinterpret_cast<const float*>(d.triangles);
+  HIP_TRY(launch_refit_records(c->stream, c->tris.as<TriMT>() + mh.rec_base, mh.recs, nullptr, r, res));
+  for (size_t lv = mh.level_ends.size(); lv-- > 0;) {  // deepest level first; the root last
+    const uint32_t lb = lv ? mh.level_ends[lv - 1] : 0u;
+    HIP_TRY(launch_refit_level(c->stream, c->nodes8.as<Node8>(), c->tris.as<TriMT>(), r.triangles, c->rf_box.as<float>(),
+                               c->rf_order.as<uint32_t>() + md.root + lb, mh.level_ends[lv] - lb, md.root, res));
+  }
+  // the mesh's new root box (24 of the result's 28 bytes): the call's only host wait
+  HIP_TRY(hipMemcpyAsync(c->rf_res_host, res, sizeof(RefitResult), hipMemcpyDeviceToHost, c->stream));
+  rc = wait_stream(c, "reading the skinned mesh's box");
+  if (rc) return rc;
+  std::memcpy(mh.bmin, c->rf_res_host->bmin, sizeof(mh.bmin));
+  std::memcpy(mh.bmax, c->rf_res_host->bmax, sizeof(mh.bmax));
+  c->inst_dirty = true;
+  c->tlas_dirty = true;
+  c->scene_epoch++;  // new geometry: kept primary hits and light visibility are stale
+  PRT_FOR_MEMBERS(prt_skin_mesh(m, mi, M, J, in_flags));
   return PRT_OK;
 }
 

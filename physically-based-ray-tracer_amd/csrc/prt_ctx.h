@@ -13,6 +13,7 @@
 #include "prt_launch.h"
 #include "prt_rccl.h"
 #include "prt_refit.h"
+#include "prt_skin_gpu.h"
 #include "prt_tlas_worker.h"
 
 namespace prt::host {
@@ -139,6 +140,16 @@ struct InstSet {
   DevBuf inst, inst_src, tlas8, tlas_slot;
   std::vector<std::pair<hipStream_t, hipEvent_t>> uses;  // the last frame that read this copy, per stream
   size_t nuse = 0;
+};
+
+// One mesh's skin binding (prt_set_mesh_skin): the bind pose as uploaded (`in`: positions, normals, joints, weights,
+// indices back to back, each part 256-byte aligned), the matrices of a call with host matrices (`mats`, 48 bytes per
+// joint) and the scratch of prt_skin_mesh (`work`: the skinned positions and normals, 16 bytes per vertex each, then
+// the fat triangles, 48 bytes per triangle).  dev: what the kernels get (matrices set per call).  Unbound: joints = 0.
+struct SkinBinding {
+  DevBuf in, mats, work;
+  SkinDev dev = {};
+  int32_t joints = 0;
 };
 
 struct MeshHost {
@@ -282,6 +293,9 @@ struct prt_ctx {
   std::vector<const float*> snap_host;
   DevBuf snap_tab;
   DevBuf aov_off, rp_off;
+  // skinning (prt_set_mesh_skin / prt_skin_mesh, prt_skin.h): one binding per mesh (empty until the first binding
+  // after a prt_set_meshes, which discards them all)
+  std::vector<prt::host::SkinBinding> skin;
 };
 
 namespace prt::host {

@@ -14,7 +14,7 @@ ABI_VERSION = 10  # PRT_ABI_VERSION of the include/prt.h these structs mirror
 FLAG_AA, FLAG_ACCUMULATE, FLAG_GAMMA, FLAG_NORMALMAP, FLAG_SKYBOX, FLAG_LIGHTED, FLAG_STOCHASTIC = (1 << i for i in range(7))
 FLAGS_DEFAULT = 0x7F
 OUT_DEVICE = 1
-IN_DEVICE = 1  # prt_update_mesh: the mesh's arrays are device memory
+IN_DEVICE = 1  # prt_update_mesh / prt_skin_mesh: the mesh's arrays / the joint matrices are device memory
 OUT_TIMED = 2  # prt_render_aov / prt_denoise: record the per-pass HIP events prt_denoise_timings reads
 DENOISE_TIMINGS = 10
 BUILDER_HOST_SAH, BUILDER_GPU_LBVH, BUILDER_HOST_SBVH, BUILDER_GPU_PLOC = 0, 1, 2, 3
@@ -39,6 +39,7 @@ EXPORTS = [
     "prt_temporal_defaults", "prt_reproject_moments", "prt_denoise_variance_defaults", "prt_denoise_variance",
     "prt_update_mesh", "prt_read_blas", "prt_read_blas_tris",
     "prt_snapshot_mesh", "prt_render_aov_deform", "prt_reproject_deform",
+    "prt_set_mesh_skin", "prt_skin_mesh",
 ]
 SHARD_ID_BYTES = 128
 SHARD_NONE, SHARD_RCCL, SHARD_GROUP = 0, 1, 2  # prt_shard_info.transport
@@ -64,6 +65,13 @@ class Mesh(C.Structure):
                 ("fixed_normals", C.c_void_p), ("fixed_uvs", C.c_void_p), ("indices", C.c_void_p),
                 ("vertices", C.c_void_p), ("face_normals", C.c_void_p), ("albedo_tex", C.c_int32),
                 ("normal_tex", C.c_int32), ("metalness_tex", C.c_int32), ("emission_tex", C.c_int32)]
+
+
+class Skin(C.Structure):
+    """prt_skin: a mesh's bind pose, four joints and weights per vertex (host arrays)."""
+    _fields_ = [("vertex_count", C.c_int32), ("tri_count", C.c_int32), ("joint_count", C.c_int32),
+                ("positions", C.c_void_p), ("normals", C.c_void_p), ("indices", C.c_void_p),
+                ("joints", C.c_void_p), ("weights", C.c_void_p)]
 
 
 class Lights(C.Structure):
@@ -173,6 +181,8 @@ def load():
         "prt_set_meshes": ([vp, C.POINTER(Mesh), i32], C.c_int),
         "prt_update_mesh": ([vp, i32, C.POINTER(Mesh), u32], C.c_int),
         "prt_snapshot_mesh": ([vp, i32], C.c_int),
+        "prt_set_mesh_skin": ([vp, i32, C.POINTER(Skin)], C.c_int),
+        "prt_skin_mesh": ([vp, i32, vp, i32, u32], C.c_int),
         "prt_read_blas": ([vp, i32, vp, C.c_uint64, C.POINTER(C.c_uint64)], C.c_int),
         "prt_read_blas_tris": ([vp, i32, vp, C.c_uint64, C.POINTER(C.c_uint64)], C.c_int),
         "prt_set_instances": ([vp, vp, vp, i32], C.c_int),

@@ -181,6 +181,8 @@ class Scene:
         self.sky = None           # (h, w, 3) float32
         self.materials = None     # per-blas material kind (_lib.MAT_*), None = all textured (Scene.cpp:193-205)
         self.areaLights = []      # at most one dict(corner, edge_u, edge_v, radiance, two_sided) (AreaLight.h)
+        self.skins = {}           # model index -> scenes.Skin (set_skin)
+        self.poses = {}           # model index -> [joints, 12] float32, the last skin_model (None: the bind pose)
 
     @classmethod
     def from_data(cls, sd):
@@ -208,6 +210,32 @@ class Scene:
         if mesh.tri_count != old.tri_count or np.asarray(mesh.vertices).size != np.asarray(old.vertices).size:
             raise ValueError("update_model: the triangle and vertex counts must stay (set_scene for a new topology)")
         self.models[index] = mesh
+        self.poses.pop(index, None)
+
+    def set_skin(self, index, skin):
+        """Model `index` is skinned from now on (`skin`: a scenes.Skin of the model's vertex count; None removes it).
+        Context.set_scene binds every skin; hand a later one to a context with Context.set_mesh_skin(index, skin), or
+        use Renderer.SetSkin, which does both."""
+        self.poses.pop(index, None)
+        if skin is None:
+            self.skins.pop(index, None)
+            return
+        if np.asarray(skin.positions).size != np.asarray(self.models[index].vertices).size:
+            raise ValueError("set_skin: the skin's vertex count differs from the model's")
+        self.skins[index] = skin
+
+    def skin_model(self, index, matrices):
+        """Model `index` takes the pose `matrices` ([joints, 12] or [joints, 3, 4] float32, row-major 3 x 4): the scene
+        keeps it, so that a later Context.set_scene poses the model again; hand it to a context with
+        Context.skin_mesh(index, matrices), or use Renderer.SkinModel, which does both.  models[index] keeps its bind
+        pose arrays."""
+        skin = self.skins.get(index)
+        if skin is None:
+            raise ValueError("skin_model: the model has no skin (set_skin)")
+        M = _f32(matrices).reshape(-1, 12).copy()
+        if len(M) != skin.joint_count:
+            raise ValueError("skin_model: the matrix count differs from the skin's joint_count")
+        self.poses[index] = M
 
 
 class Context:
@@ -283,6 +311,11 @@ class Context:
             ms[i] = _lib.Mesh(m.tri_count, m.vertices.size // 3, *[a.ctypes.data for a in arrs], m.albedo, m.normal,
                               m.metalness, m.emission)
         check(L.prt_set_meshes(self.h, ms, len(scene.models)))
+        for i, skin in getattr(scene, "skins", {}).items():  # (prt_set_meshes discarded the bindings)
+            self.set_mesh_skin(i, skin)
+            pose = getattr(scene, "poses", {}).get(i)
+            if pose is not None:
+                self.skin_mesh(i, pose)
         xf = _f32(np.stack([T for _, T in scene.blases]).reshape(-1))
         mi = np.ascontiguousarray([m for m, _ in scene.blases], np.uint32)
         check(L.prt_set_instances(self.h, xf.ctypes.data, mi.ctypes.data, len(scene.blases)))
@@ -358,6 +391,40 @@ class Context:
                 verts = arrs[4].numel() // 3
         m = _lib.Mesh(int(tri_count), int(verts), *ptrs, mesh.albedo, mesh.normal, mesh.metalness, mesh.emission)
         check(self.L.prt_update_mesh(self.h, int(index), C.byref(m), _lib.IN_DEVICE if device else 0))
+
+    def set_mesh_skin(self, index, skin):
+        """prt_set_mesh_skin: binds `skin` (a scenes.Skin; None removes the binding) to mesh `index` of the last
+        set_scene.  Checked on the host against the mesh (counts, every index, every joint); waits for the context
+        stream and may allocate."""
+        if skin is None:
+            check(self.L.prt_set_mesh_skin(self.h, int(index), None))
+            return
+        P, N = _f32(skin.positions).reshape(-1), _f32(skin.normals).reshape(-1)
+        idx = np.ascontiguousarray(skin.indices, np.int32).reshape(-1)
+        J = np.ascontiguousarray(skin.joints, np.uint16).reshape(-1)
+        Wt = _f32(skin.weights).reshape(-1)
+        V = P.size // 3
+        if N.size != P.size or J.size != 4 * V or Wt.size != 4 * V:
+            raise ValueError("set_mesh_skin: positions, normals, joints and weights differ in vertex count")
+        s = _lib.Skin(V, idx.size // 3, int(skin.joint_count), P.ctypes.data, N.ctypes.data, idx.ctypes.data,
+                      J.ctypes.data, Wt.ctypes.data)
+        check(self.L.prt_set_mesh_skin(self.h, int(index), C.byref(s)))
+
+    def skin_mesh(self, index, matrices, device=False):
+        """prt_skin_mesh: mesh `index` (bound by set_mesh_skin) is skinned with `matrices` and its BLAS refitted in
+        place, on the device.  `matrices`: [joints, 12] (or [joints, 3, 4]) float32 row-major 3 x 4, a host array; with
+        device=True a contiguous float32 torch tensor on this context's device, read in the context stream's order.
+        The call waits for the mesh's new root box."""
+        if device:
+            if not hasattr(matrices, "data_ptr") or not matrices.is_cuda or not matrices.is_contiguous() or \
+                    str(matrices.dtype) != "torch.float32" or matrices.numel() % 12:
+                raise ValueError("skin_mesh: matrices must be a contiguous torch.float32 tensor of 12 per joint on the device")
+            check(self.L.prt_skin_mesh(self.h, int(index), matrices.data_ptr(), matrices.numel() // 12, _lib.IN_DEVICE))
+            return
+        M = _f32(matrices).reshape(-1)
+        if M.size % 12:
+            raise ValueError("skin_mesh: 12 floats per joint")
+        check(self.L.prt_skin_mesh(self.h, int(index), M.ctypes.data, M.size // 12, 0))
 
     def snapshot_mesh(self, index):
         """prt_snapshot_mesh: mesh `index`'s present corner positions become its previous positions, which
@@ -915,6 +982,21 @@ class Renderer:
         show the old geometry."""
         self.scene.update_model(index, mesh)
         self.ctx.update_mesh(index, mesh)
+        self.ctx.reset_accumulation(full=True)
+
+    def SetSkin(self, index, skin):
+        """scene.models[index] is skinned from now on (a scenes.Skin; None removes it): the scene keeps the skin and the
+        context binds it (prt_set_mesh_skin).  SkinModel then poses the model."""
+        self.scene.set_skin(index, skin)
+        self.ctx.set_mesh_skin(index, skin)
+
+    def SkinModel(self, index, matrices):
+        """scene.models[index] takes the pose `matrices` ([joints, 12] float32, row-major 3 x 4): the scene keeps the
+        pose and the context skins the model and refits its BLAS on the device (prt_skin_mesh; a frame loop:
+        SkinModel, then scene.blases / TickTemporal(motion=True) or Tick).  The accumulation is reset in full, as by
+        UpdateModel."""
+        self.scene.skin_model(index, matrices)
+        self.ctx.skin_mesh(index, matrices)
         self.ctx.reset_accumulation(full=True)
 
     def CameraMoved(self):

@@ -43,6 +43,28 @@ class Mesh:
 
 
 @dataclasses.dataclass
+class Skin:
+    """A mesh's skin (prt_set_mesh_skin, csrc/prt_skin.h): the bind pose and, per vertex, four joints and four weights
+    (used as given, never renormalised; a weight of 0 still names a joint below joint_count)."""
+    positions: np.ndarray   # (V, 3) float32, bind pose
+    normals: np.ndarray     # (V, 3) float32
+    indices: np.ndarray     # (3T,) int32, the mesh's own corner indices
+    joints: np.ndarray      # (V, 4) uint16
+    weights: np.ndarray     # (V, 4) float32
+    joint_count: int
+
+    @classmethod
+    def from_mesh(cls, mesh: Mesh, joints, weights, joint_count: int) -> "Skin":
+        """The bind pose of `mesh` as it stands: its vertices, and per vertex the normal its corners carry (the
+        fixed_normals of a mesh whose corners agree per vertex, as every generator here makes them)."""
+        P = np.array(mesh.vertices, F32).reshape(-1, 3)
+        N = np.zeros_like(P)
+        N[np.asarray(mesh.indices, np.int64)] = np.asarray(mesh.fixed_normals, F32).reshape(-1, 4)[:, :3]
+        return cls(P, N, np.array(mesh.indices, np.int32).reshape(-1), np.ascontiguousarray(joints, np.uint16).reshape(-1, 4),
+                   np.ascontiguousarray(weights, F32).reshape(-1, 4), int(joint_count))
+
+
+@dataclasses.dataclass
 class Lights:
     """4 SIMD point lights (Core/Renderer.h:80-88), directionalLights[0], spotlights[0]."""
     point_pos: np.ndarray   # (4,3)
