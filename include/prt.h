@@ -113,7 +113,10 @@ typedef struct {
 /* One emitting parallelogram corner + a*edge_u + b*edge_v (a, b in [0,1]) -- an extension: the reference's
  * AreaLight (Core/AreaLight.h) is never sampled by Trace.  Radiance on the side of cross(edge_u, edge_v)
  * (both sides when two_sided); sampled by next-event estimation at every lit hit and reached by BRDF rays,
- * combined with the power heuristic. */
+ * combined with the power heuristic.  At a path's last segment the light sample is unweighted:
+ * no BRDF ray follows there, so light sampling is the only strategy.  The BRDF strategy's integrand is the
+ * reference's indirect weights (evalIndirectCombinedBRDF: (1, 1, 1) for the specular lobe), not evalCombinedBRDF,
+ * so with more than one bounce the light's term is not the integral of evalCombinedBRDF over the light. */
 typedef struct {
     float corner[3], edge_u[3], edge_v[3];
     float radiance[3];

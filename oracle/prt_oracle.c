@@ -1036,7 +1036,8 @@ static f3 trace_ext(const orc_scene* s, const orc_params* P, ray_t r, int depth,
         if (cos_l > 0.0f && dot3(N, L) > 0.0f) {
             const float pl = dsq / (s->al[15] * cos_l);
             const float pb = brdf_pdf(&m, N, V, L, brdf_probability(&m, V, N));
-            const float w = mis_power(pl, pb);
+            /* at the path's last segment (:329) no BRDF ray follows: the light sample is the only strategy, unweighted */
+            const float w = (depth == P->bounces - 1) ? 1.0f : mis_power(pl, pb);
             const f3 f = mul3(eval_combined(N, L, V, &m), muls(v3(s->al[12], s->al[13], s->al[14]), w / pl));
             const ray_t sr = make_ray(add3(I, muls(L, EPSILON)), L);
             cnt->shadow++;

@@ -328,9 +328,11 @@ PRT_HD bool delta_lobe(const Material& m) { return m.metal == 1.0f && m.rough ==
 
 
 // next-event estimation of the area light at a shaded hit: false when the sample faces away (no ray);
-// else the shadow ray, its tmax and the unoccluded contribution BRDF * Le * w_light / p_light
+// else the shadow ray, its tmax and the unoccluded contribution BRDF * Le * w_light / p_light.
+// last: the hit is the path's last segment (:329), which no BRDF ray follows: the light sample is the only strategy
+// there and w_light = 1
 __device__ __forceinline__ bool area_nee(const AreaLight& A, V3 I, V3 N, V3 V, const Material& m, float xi1, float xi2,
-                                         Ray& sr, float& tmax, V3& f) {
+                                         bool last, Ray& sr, float& tmax, V3& f) {
   const V3 y = A.p0 + xi1 * A.eu + xi2 * A.ev;
   V3 L = y - I;
   const float dsq = dot(L, L);
@@ -341,7 +343,7 @@ __device__ __forceinline__ bool area_nee(const AreaLight& A, V3 I, V3 N, V3 V, c
   if (!(cos_l > 0.0f) || !(dot(N, L) > 0.0f)) return false;
   const float pl = dsq / (A.area * cos_l);
   const float pb = brdf_pdf(m, N, V, L, brdf_probability(m, V, N));
-  const float w = mis_power(pl, pb);
+  const float w = last ? 1.0f : mis_power(pl, pb);
   f = eval_combined_brdf(N, L, V, m) * (A.le * (w / pl));
   sr = make_ray(I + L * kEpsilon, L);
   tmax = dist - kEpsilon;

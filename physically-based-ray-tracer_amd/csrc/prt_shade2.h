@@ -218,7 +218,7 @@ __device__ __forceinline__ ShadedHit shade_hit(const SceneDev& S, const TraceArg
       Ray sr;
       float tmax;
       V3 fa;
-      if (area_nee(area_light(S), I, ha.N, V, ha.m, xi1, xi2, sr, tmax, fa)) {
+      if (area_nee(area_light(S), I, ha.N, V, ha.m, xi1, xi2, (int)depth == A.bounces - 1, sr, tmax, fa)) {
         area_ray = true;
         B.ao[item] = make_float4(sr.O.x, sr.O.y, sr.O.z, tmax);
         B.ad[item] = make_float4(sr.D.x, sr.D.y, sr.D.z, 0.0f);

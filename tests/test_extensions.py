@@ -128,6 +128,18 @@ def test_extensions_match_oracle(gpu_ctx, case, flags):
 
 
 @pytest.mark.gpu
+def test_area_light_seen_directly_device(gpu_ctx):
+    """The device twin of test_area_light_seen_directly: the centre pixel is exactly sqrt(Le)."""
+    W, H = 48, 32
+    sd = scenes.with_extensions(_base(), area_light=_facing_light())
+    gpu_scene(gpu_ctx, sd, W, H)
+    avg, _, st = gpu_ctx.render(W, H, 1, 3, NO_AA)
+    c = (H // 2) * W + W // 2
+    assert np.array_equal(avg[c, :3], np.sqrt(np.asarray([3.0, 2.0, 1.0], F32)))
+    assert st.segments >= W * H
+
+
+@pytest.mark.gpu
 def test_extensions_tiles_match_full_frame(gpu_ctx):
     """Pixel-tile sharding with dielectric + mirror + area light: one rank's tiles equal the full frame."""
     import torch
