@@ -643,7 +643,8 @@ void build_wide8(const float* triangles, int32_t T, int max_leaf, Out& out, bool
     uint32_t nextchild = nd.child_base, tri_off = 0;
     for (int s = 0; s < 8; s++) {
       const int i = child_in[s];
-      if (i < 0) {  // empty slot: inverted box never hits
+      if (i < 0) {  // unoccupied slot: meta 0, imask bit clear.  The inverted box is a hint only -- far from a small
+                    // node the slab test passes it too; occupancy decides (prt_node8.h)
         Fmt::empty(nd, s);
         continue;
       }

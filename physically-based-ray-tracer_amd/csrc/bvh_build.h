@@ -27,6 +27,10 @@ static_assert(sizeof(TriMT) == 48, "TriMT must be 48 bytes");
 //   [1]  child_base tri_base meta[8]    interior slot k -> child_base + popc(imask & ((1<<k)-1));
 //                                       leaf slot k: meta = (tri offset << 3) | count (count 1..4)
 //   [2-4] qlo{x,y,z}[8] qhi{x,y,z}[8]   child bounds quantised outward on the node grid
+// A slot is occupied when its imask bit is set or its count (meta & 7) is not 0.  An unoccupied slot has meta 0, its
+// imask bit clear and the inverted box qlo = 255, qhi = 0.  The inverted box is a hint, not the contract: once the
+// node's extent is below about half an ulp of a ray's distance to it, fma(q, b, a) absorbs q and the slab test passes
+// every slot, so a traversal must not act on a slot because its box was hit -- occupancy decides (prt_node8.h).
 // Children sit in slots chosen per octant (slot s holds the child nearest for rays of octant s), so
 // visiting slots in the order (i ^ ray_octant) is approximately front to back without sorting.
 struct alignas(16) Node8 {

@@ -656,7 +656,8 @@ __device__ __forceinline__ void collapse_task(const Task tk, const float4* __res
   uint32_t nextchild = nd.child_base, tri_off = 0, tslot = tbase;
   for (int s = 0; s < 8; s++) {
     const int i = child_in[s];
-    if (i < 0) {
+    if (i < 0) {  // unoccupied slot: meta 0, imask bit clear; the inverted box is a hint only, occupancy decides
+                  // (bvh_build.h, prt_node8.h)
       nd.qlox[s] = nd.qloy[s] = nd.qloz[s] = 255;
       nd.qhix[s] = nd.qhiy[s] = nd.qhiz[s] = 0;
       continue;

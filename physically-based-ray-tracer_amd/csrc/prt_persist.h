@@ -202,10 +202,11 @@ __device__ __forceinline__ void trav8_persistent_t(const SceneDev& S, uint32_t* 
     const uint4* np = top ? reinterpret_cast<const uint4*>(S.tlas8 + node) : blas_node(S.nodes8, node);
     const uint4 a = np[0], b = np[1];
     const uint4 c = np[2], d = np[3], e = np[4];
-    const uint32_t hits = node8_hits(a, c, d, e, O, rD, tlimit);
+    const uint32_t hits = node8_slabs(a, c, d, e, O, rD, tlimit);
     const uint32_t imask = a.w >> 24;
     if (TLAS && top) {  // instance children: one group addressed by slot (tlas_slot[b.y + slot])
-      const uint32_t ih = hits & imask, lh = hits & ~imask;
+      // occupied slots only (prt_node8.h): an unoccupied slot's tlas_slot entry names no instance
+      const uint32_t ih = hits & imask, lh = hits & ~imask & node8_occupied(a, b);
       if (ih) {
         push_cur();
         gbase = b.x; gmask = order_mask(ih, oct); gimask = imask;
@@ -226,15 +227,16 @@ __device__ __forceinline__ void trav8_persistent_t(const SceneDev& S, uint32_t* 
     if (tcnt == 0) {
       const uint32_t k = __builtin_ctz(lhit);
       lhit &= lhit - 1u;
-      const uint32_t meta = ((k < 4 ? lmeta0 : lmeta1) >> (8 * (k & 3))) & 0xFFu;
-      tcur = ltri + (meta >> 3);
-      tcnt = meta & 7u;
+      (void)node8_leaf(ltri, lmeta0, lmeta1, k, tcur, tcnt);
     }
+    // the slab mask may name an unoccupied slot (prt_node8.h): its count is 0, there is no record to test and no
+    // count to take one off.  Without a branch: the step reads record 0 and drops the result
+    const bool live = tcnt != 0u;
     float t, u, v;
     uint32_t prim;
-    const bool hit = mt_test(S.tris + tcur, O, D, t, u, v, prim);
+    const bool hit = mt_test(S.tris + (live ? tcur : 0u), O, D, t, u, v, prim) && live;
     tcur++;
-    tcnt--;
+    tcnt -= live ? 1u : 0u;
     if (MODE == 1 || (MODE == 2 && any)) {
       if (hit && t < h.t) {  // tiny_bvh.h:6594 (h.t holds tmax)
         node = kNoNode; lhit = 0; tcnt = 0;

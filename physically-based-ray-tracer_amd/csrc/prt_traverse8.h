@@ -7,6 +7,7 @@
 // has interior hits while the current group still has unvisited children, so the stack never holds
 // more than one entry per tree level.
 #pragma once
+#include "prt_node8.h"
 #include "prt_traverse.h"
 
 namespace prt {
@@ -17,44 +18,8 @@ struct Slab8 {
   float bx, by, bz;  // 2^(e-127) * rD  (exact: power-of-two scale)
 };
 
-__device__ __forceinline__ float byte_f(uint32_t w, int k) { return (float)((w >> (8 * k)) & 0xFFu); }
-
-// hit mask (physical slots) of the 8 children; near/far plane choice by the sign of rD
-__device__ __forceinline__ uint32_t node8_hits(const uint4& a, const uint4& c, const uint4& d, const uint4& e,
-                                               const V3& O, const V3& rD, float tlimit) {
-  const float sx = __uint_as_float((a.w & 0xFFu) << 23), sy = __uint_as_float(((a.w >> 8) & 0xFFu) << 23),
-              sz = __uint_as_float(((a.w >> 16) & 0xFFu) << 23);
-  const float ax = (__uint_as_float(a.x) - O.x) * rD.x, ay = (__uint_as_float(a.y) - O.y) * rD.y,
-              az = (__uint_as_float(a.z) - O.z) * rD.z;
-  const float bx = sx * rD.x, by = sy * rD.y, bz = sz * rD.z;
-  // near / far quantised planes per axis: words (lo0-3, lo4-7) / (hi0-3, hi4-7)
-  const bool px = rD.x >= 0.0f, py = rD.y >= 0.0f, pz = rD.z >= 0.0f;
-  const uint32_t nx0 = px ? c.x : d.z, nx1 = px ? c.y : d.w, fx0 = px ? d.z : c.x, fx1 = px ? d.w : c.y;
-  const uint32_t ny0 = py ? c.z : e.x, ny1 = py ? c.w : e.y, fy0 = py ? e.x : c.z, fy1 = py ? e.y : c.w;
-  const uint32_t nz0 = pz ? d.x : e.z, nz1 = pz ? d.y : e.w, fz0 = pz ? e.z : d.x, fz1 = pz ? e.w : d.y;
-  uint32_t hits = 0;
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    const int b = k & 3;
-    const uint32_t wnx = k < 4 ? nx0 : nx1, wny = k < 4 ? ny0 : ny1, wnz = k < 4 ? nz0 : nz1;
-    const uint32_t wfx = k < 4 ? fx0 : fx1, wfy = k < 4 ? fy0 : fy1, wfz = k < 4 ? fz0 : fz1;
-    const float tnx = __builtin_fmaf(byte_f(wnx, b), bx, ax), tfx = __builtin_fmaf(byte_f(wfx, b), bx, ax);
-    const float tny = __builtin_fmaf(byte_f(wny, b), by, ay), tfy = __builtin_fmaf(byte_f(wfy, b), by, ay);
-    const float tnz = __builtin_fmaf(byte_f(wnz, b), bz, az), tfz = __builtin_fmaf(byte_f(wfz, b), bz, az);
-    const float tn = fmaxf(fmaxf(tnx, tny), fmaxf(tnz, 0.0f)) * kPadRatio;  // both pads (prt_traverse.h)
-    const float tf = fminf(fminf(tfx, tfy), tfz);
-    if (tn <= tf && tn <= tlimit) hits |= 1u << k;
-  }
-  return hits;
-}
-
-// physical-slot mask -> traversal-order mask (bit k ^ oct)
-__device__ __forceinline__ uint32_t order_mask(uint32_t m, uint32_t oct) {
-  if (oct & 1u) m = ((m & 0x55u) << 1) | ((m >> 1) & 0x55u);
-  if (oct & 2u) m = ((m & 0x33u) << 2) | ((m >> 2) & 0x33u);
-  if (oct & 4u) m = ((m & 0x0Fu) << 4) | ((m >> 4) & 0x0Fu);
-  return m;
-}
+// node8_slabs, node8_hits, order_mask, node8_leaf: prt_node8.h (shared with the host), with the rule that no
+// traversal acts on an unoccupied slot and where each traversal enforces it.
 
 // One lane's traversal stack: levels [0, STACK) in LDS (stk[2 * level * BLOCK], one column per lane), deeper
 // levels in the lane's HBM spill column (S.spill, level-major so a wave's entries of one level are contiguous;
@@ -118,13 +83,13 @@ __device__ __forceinline__ bool blas_traverse8(const Node8* __restrict__ nodes, 
       const uint4* np = blas_node(nodes, node);
       const uint4 a = np[0], b = np[1];
       const uint32_t imask = a.w >> 24;
-      const uint32_t hits = node8_hits(a, np[2], np[3], np[4], O, rD, h.t);
+      const uint32_t hits = node8_slabs(a, np[2], np[3], np[4], O, rD, h.t);
       uint32_t lhit = hits & ~imask;
       while (lhit) {  // leaf children: test their triangles now
         const uint32_t k = __builtin_ctz(lhit);
         lhit &= lhit - 1u;
-        const uint32_t meta = ((k < 4 ? b.z : b.w) >> (8 * (k & 3))) & 0xFFu;
-        const uint32_t first = b.y + (meta >> 3), cnt = meta & 7u;
+        uint32_t first, cnt;
+        (void)node8_leaf(b.y, b.z, b.w, k, first, cnt);  // an unoccupied slot the slab mask named: cnt = 0
         for (uint32_t i = 0; i < cnt; i++) {
           float t, u, v;
           uint32_t prim;
@@ -179,7 +144,7 @@ __device__ __forceinline__ bool tlas_traverse8(const SceneDev& S, const Ray& r, 
       const uint4* np = reinterpret_cast<const uint4*>(S.tlas8 + node);
       const uint4 a = np[0], b = np[1];
       const uint32_t imask = a.w >> 24;
-      const uint32_t hits = node8_hits(a, np[2], np[3], np[4], r.O, r.rD, h.t);
+      const uint32_t hits = node8_hits(a, b, np[2], np[3], np[4], r.O, r.rD, h.t);
       uint32_t lh = order_mask(hits & ~imask, oct);
       while (lh) {  // instances of this node, near to far
         const uint32_t k = __builtin_ctz(lh) ^ oct;

@@ -9,7 +9,7 @@ __global__ void k_isa_node8(const Node8* __restrict__ nodes, const float* __rest
   const uint32_t i = threadIdx.x;
   const uint4* np = reinterpret_cast<const uint4*>(nodes + i);
   const V3 O = v3(ray[0], ray[1], ray[2]), rD = v3(ray[3], ray[4], ray[5]);
-  out[i] = node8_hits(np[0], np[2], np[3], np[4], O, rD, ray[6]);
+  out[i] = node8_slabs(np[0], np[2], np[3], np[4], O, rD, ray[6]);
 }
 
 __global__ void k_isa_tri(const TriMT* __restrict__ tris, const float* __restrict__ ray, float* out) {

@@ -1,4 +1,5 @@
-// trav_stats.cpp -- host replica of the Node8 BLAS traversal (prt_traverse8.h) with visit counters and a
+// trav_stats.cpp -- host replica of the Node8 BLAS traversal (prt_traverse8.h; its node visit is the product's own,
+// prt_node8.h) with visit counters and a
 // lock-step wave64 model, to size traversal-kernel changes before spending GPU time.  Diagnostic only.
 //
 // input:  <tris.bin>  float32 fat triangles (Model::triangles layout: 3 x float4 per triangle)
@@ -8,7 +9,7 @@
 //         kind on stderr); with --models the lock-step wave cost (iterations = max over lanes), lane
 //         efficiency with and without per-lane ray refill, and the decoupled node/triangle model.
 //
-// build:  g++ -O2 -I physically-based-ray-tracer_amd/csrc scripts/trav_stats.cpp
+// build:  g++ -O2 -ffp-contract=off -I physically-based-ray-tracer_amd/csrc scripts/trav_stats.cpp
 //             physically-based-ray-tracer_amd/csrc/bvh_build.cpp -o /tmp/trav_stats
 #include <algorithm>
 #include <cmath>
@@ -18,13 +19,14 @@
 #include <vector>
 
 #include "bvh_build.h"
+#include "prt_node8.h"
 
 using namespace prt;
 
 namespace {
 
 struct V { float x, y, z; };
-const float kFar = 1e30f, kNearPad = 0.99999f, kFarPad = 1.00001f;
+const float kFar = 1e30f;
 float safercp(float x) { return x > 1e-12f ? 1.0f / x : (x < -1e-12f ? 1.0f / x : kFar); }
 
 bool mt(const TriMT& T, V O, V D, float& t) {
@@ -38,13 +40,6 @@ bool mt(const TriMT& T, V O, V D, float& t) {
   const float v = (D.x * qx + D.y * qy + D.z * qz) * id;
   t = (T.e2[0] * qx + T.e2[1] * qy + T.e2[2] * qz) * id;
   return u >= 0 && u <= 1 && v >= 0 && u + v <= 1 && t > 0;
-}
-
-uint32_t order_mask(uint32_t m, uint32_t oct) {
-  if (oct & 1u) m = ((m & 0x55u) << 1) | ((m >> 1) & 0x55u);
-  if (oct & 2u) m = ((m & 0x33u) << 2) | ((m >> 2) & 0x33u);
-  if (oct & 4u) m = ((m & 0x0Fu) << 4) | ((m >> 4) & 0x0Fu);
-  return m;
 }
 
 // one lane's traversal as a list of iterations: tri tests done in each node visit
@@ -61,22 +56,10 @@ Trace traverse(const BuiltBlas8& B, V O, V D, float tmax, bool any) {
   while (true) {
     const Node8& n = B.nodes[node];
     if (!g_visits.empty()) g_visits[node]++;
-    const float sc[3] = {std::ldexp(1.0f, (int)n.ex - 127), std::ldexp(1.0f, (int)n.ey - 127),
-                         std::ldexp(1.0f, (int)n.ez - 127)};
-    const float ax = (n.px - O.x) * rD.x, ay = (n.py - O.y) * rD.y, az = (n.pz - O.z) * rD.z;
-    const float bx = sc[0] * rD.x, by = sc[1] * rD.y, bz = sc[2] * rD.z;
-    uint32_t hits = 0;
-    for (int k = 0; k < 8; k++) {
-      const float lx = std::fma((float)(rD.x >= 0 ? n.qlox[k] : n.qhix[k]), bx, ax);
-      const float hx = std::fma((float)(rD.x >= 0 ? n.qhix[k] : n.qlox[k]), bx, ax);
-      const float ly = std::fma((float)(rD.y >= 0 ? n.qloy[k] : n.qhiy[k]), by, ay);
-      const float hy = std::fma((float)(rD.y >= 0 ? n.qhiy[k] : n.qloy[k]), by, ay);
-      const float lz = std::fma((float)(rD.z >= 0 ? n.qloz[k] : n.qhiz[k]), bz, az);
-      const float hz = std::fma((float)(rD.z >= 0 ? n.qhiz[k] : n.qloz[k]), bz, az);
-      const float tn = std::max(std::max(lx, ly), std::max(lz, 0.0f)) * kNearPad;
-      const float tf = std::min(std::min(hx, hy), hz) * kFarPad;
-      if (tn <= tf && tn <= ht) hits |= 1u << k;
-    }
+    // the product's visit (prt_node8.h): occupied slots whose padded slab interval the ray meets
+    Node8Word w[5];
+    std::memcpy(w, &n, sizeof(w));
+    const uint32_t hits = node8_hits(w[0], w[1], w[2], w[3], w[4], O, rD, ht);
     int ntri = 0;
     bool done = false;
     uint32_t lhit = hits & ~(uint32_t)n.imask;

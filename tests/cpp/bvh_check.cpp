@@ -59,7 +59,7 @@ static int fail(const char* what, long a, long b) {
 //   structure   every node is reached exactly once (no node with two parents, no orphan); an interior child's index
 //               is in range and greater than its parent's; a leaf slot's count is 1..max_leaf and its range in
 //               bounds; every record lies in the range of exactly one slot; a slot that is neither interior nor leaf
-//               has meta 0
+//               (imask bit clear, count 0) has meta 0 and the inverted box qlo = 255, qhi = 0
 //   coverage    every primitive is referenced (exactly once, and prim < T, without spatial splits)
 //   containment the traversal culls at every ancestor slot, each quantised on its own node's grid: a referenced
 //               triangle lies inside its leaf slot's dequantised box and inside the intersection of that box with the
@@ -120,6 +120,10 @@ struct TreeCheck {
       const uint32_t cnt = n.meta[s] & 7u;
       if (!inner && cnt == 0) {
         if (n.meta[s]) return bad("empty slot with nonzero meta", (long)j, s);
+        // the inverted box: a hint only (occupancy decides, prt_node8.h), but the builders and the refit all write it
+        const uint8_t* q[6] = {n.qlox, n.qloy, n.qloz, n.qhix, n.qhiy, n.qhiz};
+        for (int k = 0; k < 3; k++)
+          if (q[k][s] != 255 || q[3 + k][s] != 0) return bad("empty slot without the inverted box", (long)j, s);
         continue;
       }
       double lo[3], hi[3], clo[3], chi[3];

@@ -194,6 +194,16 @@ def _orphan(t):
     s = t.interior(j)[-1][0]
     t.nodes[j, 15] &= np.uint8(~(1 << s) & 0xFF)
     assert t.nodes[j, 24 + s] == 0
+    t.nodes[j, [32 + s, 40 + s, 48 + s]] = 255  # emptied as a builder empties a slot: the inverted box qlo = 255,
+    t.nodes[j, [56 + s, 64 + s, 72 + s]] = 0    # qhi = 0 (without it the checker stops at the slot itself, below)
+
+
+def _not_inverted(t):
+    """An interior slot's imask bit cleared and nothing else: an unoccupied slot (meta 0) that kept a real box."""
+    j = next(j for j in range(len(t.nodes)) if t.interior(j))
+    s = t.interior(j)[-1][0]
+    t.nodes[j, 15] &= np.uint8(~(1 << s) & 0xFF)
+    assert t.nodes[j, 24 + s] == 0 and t.nodes[j, 32 + s] <= t.nodes[j, 56 + s]
 
 
 def _overlap(t):
@@ -224,6 +234,7 @@ DEFECTS = {
     "duplicate_prim": (_duplicate_prim, 0, "primitive in several leaves"),
     "shared_children": (_shared_children, 0, "node reached twice"),
     "orphan": (_orphan, 0, "node not reached from the root"),
+    "not_inverted": (_not_inverted, 0, "empty slot without the inverted box"),
     "overlap": (_overlap, 0, "record in two leaf ranges"),
     "count_4": (_count_4, 0, "leaf count above the maximum"),
     "depth_plus": (lambda t: None, 1, "reported depth differs"),

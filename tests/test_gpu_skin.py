@@ -55,13 +55,14 @@ def _scene(name):
 _SETUPS = {}
 _ORACLE = {}
 # Where the pose `flat` collapses what follows joint 0 alone: a point off the camera's axis and a few units from every
-# coordinate plane.  Not the origin, for a reason that has nothing to do with skinning: the scenes' cameras look at the
-# origin, the first AA sample of the centre pixel travels exactly through it, and a BLAS node whose whole extent is the
-# 2e-7 of an inflated point at the origin is smaller than half an ulp of the ray's distance to it.  There the slab
-# test's fma(255, b, a) rounds to a, the inverted box of an empty child slot (255 .. 0) no longer misses, and the
-# wavefront traversal's triangle step (prt_persist.h tri_step) takes that slot's count of 0 for a count, which
-# underflows -- with prt_update_mesh or prt_set_meshes of the same arrays as well.  A box around a point p is inflated
-# by |p| * 1e-6, so a few units away the node is some 1e-6 wide and the test is exact again.
+# coordinate plane.  The pose `flat0` collapses into the origin instead, the point the scenes' cameras look at: the
+# first AA sample of the centre pixel travels exactly through it, and a BLAS node whose whole extent is the 2e-7 of an
+# inflated point at the origin is smaller than half an ulp of the ray's distance to it.  There the slab test's
+# fma(255, b, a) rounds to a and the inverted box of an unoccupied child slot (255 .. 0) no longer misses; a node
+# visit hands on occupied slots only (prt_node8.h), so the pose renders like any other (before that rule the
+# wavefront traversal's triangle step took such a slot's count of 0 for a count, which underflowed).  A box around a
+# point p is inflated by |p| * 1e-6, so a few units away the node is some 1e-6 wide and the slab test is exact again:
+# `flat` never met the condition, and stays as the ordinary case.
 COLLAPSE_POINT = (-2.5, 1.0, 1.5)
 
 
@@ -87,8 +88,8 @@ class Setup:
 
 def setup(name, J=3):
     """The scene `name` with its mesh bound to J joints (above 8: seven of them used, the first and the last among
-    them) and the poses m1, m2 (ordinary), x2 (every joint doubles the extent) and flat (the first joint collapses what
-    follows it alone, into COLLAPSE_POINT)."""
+    them) and the poses m1, m2 (ordinary), x2 (every joint doubles the extent), flat (the first joint collapses what
+    follows it alone, into COLLAPSE_POINT) and flat0 (the same into the origin)."""
     if (name, J) not in _SETUPS:
         sd, mi = _scene(name)
         mesh = sd.meshes[mi]
@@ -101,6 +102,8 @@ def setup(name, J=3):
              "x2": np.tile(skin_ref.rigid(scale=2.0), (J, 1))}
         M["flat"] = M["m1"].copy()
         M["flat"][0] = (0, 0, 0, -2.5, 0, 0, 0, 1.0, 0, 0, 0, 1.5)  # see COLLAPSE_POINT
+        M["flat0"] = M["m1"].copy()
+        M["flat0"][0] = 0.0  # into the origin
         _SETUPS[(name, J)] = Setup(sd, mi, skin, M)
     return _SETUPS[(name, J)]
 
@@ -244,6 +247,18 @@ def test_collapsed_triangles_render_as_update_mesh_does():
     assert 0 < z.sum() < z.size and np.array_equal(s.R("flat").fixed_normals.reshape(-1, 4)[3 * np.flatnonzero(z)[0], :3],
                                                    [0, 1, 0])
     skinned_equals_updated(s, "flat", key=("small", 3, "flat"))
+
+
+def test_collapse_into_the_origin_renders_as_update_mesh_does():
+    """The pose that could not be tested before a node visit skipped unoccupied slots (see COLLAPSE_POINT): what
+    follows joint 0 alone collapses into the point the camera looks at."""
+    s = setup("small")
+    R = s.R("flat0")
+    z = ~R.face_normals.reshape(-1, 3).any(axis=1)
+    assert 0 < z.sum() < z.size
+    at_origin = ~np.asarray(R.triangles, F32).reshape(-1, 3, 4)[:, :, :3].any(axis=(1, 2))
+    assert at_origin.sum() >= 100 and not (at_origin & ~z).any()  # whole triangles sit at the origin, exactly
+    skinned_equals_updated(s, "flat0", key=("small", 3, "flat0"))
 
 
 def test_device_matrices_give_the_same_bytes_and_frames():
