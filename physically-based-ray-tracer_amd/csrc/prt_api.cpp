@@ -1,13 +1,13 @@
-// prt_api.cpp -- C-ABI implementation (include/prt.h): device residency of the scene, BLAS build,
-// the queries.  One host thread per context; all device work on one HIP stream.  The context itself is prt_ctx.h;
-// the render path (prt_render and what it calls) is prt_api_render.cpp, the image-space passes (denoisers,
-// reprojections) are prt_api_image.cpp.
+// prt_api.cpp -- C-ABI implementation (include/prt.h): the context, device residency of the scene (textures,
+// instances, lights, camera, sky), the queries, the AOVs, the shards.  One host thread per context; all device work
+// on one HIP stream.  The context itself is prt_ctx.h; the mesh entry points (BLAS build, in-place update, skinning,
+// snapshots, read-back) are prt_api_mesh.cpp, the render path (prt_render and what it calls) is prt_api_render.cpp,
+// the image-space passes (denoisers, reprojections) are prt_api_image.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -16,8 +16,6 @@
 #include <vector>
 
 #include "bvh_build.h"
-#include "bvh_gpu.h"
-#include "prt_blas_refit.h"
 #include "prt_ctx.h"
 #include "prt_deform.h"
 #include "prt_denoise.h"
@@ -116,22 +114,22 @@ int prt::host::rccl_wait(prt_ctx* c, hipStream_t s, const char* what) {
   return PRT_OK;
 }
 
-// finish the frames queued on the context stream (and the frames in flight) before a setter overwrites (or frees)
-// resident buffers
-int prt::host::drain(prt_ctx* c) {
-  const int rc = join_flights(c);
-  if (rc) return rc;
-  HIP_TRY(hipSetDevice(c->device));
-  if (c->sh_kind == 1 && c->comm) return rccl_wait(c, c->stream, "waiting for the context's frames");
+// wait for the context stream (bounded on an RCCL-sharded context)
+int prt::host::wait_stream(prt_ctx* c, const char* what) {
+  if (c->sh_kind == 1 && c->comm) return rccl_wait(c, c->stream, what);
   HIP_TRY(hipStreamSynchronize(c->stream));
   return PRT_OK;
 }
 
-namespace {
+// finish the frames queued on the context stream (and the frames in flight) before a setter overwrites (or frees)
+// resident buffers
+int prt::host::drain(prt_ctx* c) {
+  PRT_JOIN(c);
+  HIP_TRY(hipSetDevice(c->device));
+  return wait_stream(c, "waiting for the context's frames");
+}
 
-// triangles per leaf slot the builders may form (binary SAH leaves and the collapse's leaf slots; 2 / 4 measured
-// no better on C4)
-int max_leaf_tris() { return 3; }
+namespace {
 
 // waves/SIMD of the persistent traversal kernels: the LDS stack (9 / 11 / 14 / 18 groups at 7 / 6 / 5 / 4
 // waves) must hold max_depth - 1 groups; deeper BVHs (depth_ok caps them at kMaxBvhDepth = 64 levels) run the
@@ -270,8 +268,7 @@ int ensure_instances(prt_ctx* c) {
   const size_t cap_nodes = (size_t)std::max(n, 1);
   if (X.inst.bytes < sizeof(InstDev) * cap || X.inst_src.bytes < sizeof(InstSrc) * cap ||
       (use_tlas && (X.tlas8.bytes < cap_nodes * sizeof(Node8) || X.tlas_slot.bytes < cap_nodes * 32))) {
-    const int rc = drain(c);
-    if (rc) return rc;
+    PRT_TRY(drain(c));
     HIP_TRY(X.inst.ensure(sizeof(InstDev) * cap));
     HIP_TRY(X.inst_src.ensure(sizeof(InstSrc) * cap));
     if (use_tlas) {
@@ -305,8 +302,7 @@ int ensure_instances(prt_ctx* c) {
     }
   }
   StageSlot* st = nullptr;
-  int rc = stage_acquire(c, sb_src + sb_nodes + sb_slot, st);
-  if (rc) return rc;
+  PRT_TRY(stage_acquire(c, sb_src + sb_nodes + sb_slot, st));
   char* hp = static_cast<char*>(st->p);
   st->lost = true;  // until the copies out of it are enqueued (a failure below leaves it out of the pool)
   std::memcpy(hp, src.data(), sb_src);  // (the worker reads the sources from here)
@@ -336,8 +332,7 @@ int ensure_instances(prt_ctx* c) {
     HIP_TRY(hipMemcpyAsync(X.tlas8.p, cur.tlas8.p, cap_nodes * sizeof(Node8), hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(X.tlas_slot.p, cur.tlas_slot.p, cap_nodes * 32, hipMemcpyDeviceToDevice, c->stream));
   }
-  rc = stage_release(c, *st, c->stream);
-  if (rc) return rc;
+  PRT_TRY(stage_release(c, *st, c->stream));
   st->lost = false;
   c->use_tlas = use_tlas;
   if (!use_tlas) {
@@ -391,8 +386,7 @@ int prt::host::ensure_spill(prt_ctx* c, SceneDev& S, size_t threads) {
   if (levels <= 0) return PRT_OK;
   const size_t need = sizeof(uint2) * (size_t)levels * std::max<size_t>(threads, (size_t)kSpillTraceBlocks * 64u);
   if (c->spill.bytes < need) {
-    const int rc = drain(c);
-    if (rc) return rc;
+    PRT_TRY(drain(c));
     HIP_TRY(c->spill.ensure(need));
   }
   S.spill = c->spill.as<uint2>();
@@ -403,8 +397,7 @@ int prt::host::ensure_spill(prt_ctx* c, SceneDev& S, size_t threads) {
 int prt::host::scene_ready(prt_ctx* c, SceneDev& S) {
   if (c->mesh_host.empty()) return fail(PRT_ERR_NOT_READY, "no meshes: call prt_set_meshes");
   if (c->inst_mesh.empty()) return fail(PRT_ERR_NOT_READY, "no instances: call prt_set_instances");
-  int rc = ensure_instances(c);
-  if (rc) return rc;
+  PRT_TRY(ensure_instances(c));
   std::memset(&S, 0, sizeof(S));
   S.diag = c->diag.as<uint32_t>();
   S.nodes8 = c->nodes8.as<Node8>();
@@ -468,120 +461,6 @@ PostDev prt::host::post_params(const prt_ctx* c, int32_t W, int32_t H) {
   P.H = H;
   return P;
 }
-
-namespace {
-
-// a setter of a local group applies to every member (member 0 = the group context itself)
-#define PRT_FOR_MEMBERS(call)                 \
-  do {                                         \
-    for (prt_ctx* m : c->members) {            \
-      const int rc_ = (call);                  \
-      if (rc_) return rc_;                     \
-    }                                          \
-  } while (0)
-
-// ---- prt_update_mesh: scratch, tree levels, staging (the refit itself: prt_blas_refit.h / prt_blas_refit.hip)
-
-// wait for the context stream (bounded on an RCCL-sharded context, as drain())
-int wait_stream(prt_ctx* c, const char* what) {
-  if (c->sh_kind == 1 && c->comm) return rccl_wait(c, c->stream, what);
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return PRT_OK;
-}
-
-// byte offsets of a mesh's six arrays (prt_mesh order) in the staging buffers of host-array updates
-struct RefitStage {
-  size_t off[6], bytes[6], total;
-};
-RefitStage refit_stage(size_t T, size_t V) {
-  RefitStage r;
-  const size_t b[6] = {48 * T, 48 * T, 24 * T, 12 * T, 12 * V, 12 * T};
-  size_t at = 0;
-  for (int k = 0; k < 6; k++) {
-    r.off[k] = at;
-    r.bytes[k] = b[k];
-    at += (b[k] + 255) & ~size_t(255);
-  }
-  r.total = at;
-  return r;
-}
-
-// The scratch of the scene as it stands, allocated by the first update after a prt_set_meshes (which drained the
-// context, so nothing queued reads what a larger allocation replaces) and kept: later updates allocate nothing.
-int refit_scratch(prt_ctx* c, bool host_arrays) {
-  size_t nodes = 0, stage = 0;
-  for (const MeshHost& m : c->mesh_info) {
-    nodes += (size_t)m.nodes;
-    stage = std::max(stage, refit_stage((size_t)m.tris, (size_t)m.verts).total);
-  }
-  HIP_TRY(c->rf_box.ensure(24 * nodes));
-  HIP_TRY(c->rf_order.ensure(4 * nodes));
-  HIP_TRY(c->rf_res.ensure(sizeof(RefitResult)));
-  if (!c->rf_res_host)
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->rf_res_host), sizeof(RefitResult), hipHostMallocDefault));
-  if (!c->rf_ev) HIP_TRY(hipEventCreateWithFlags(&c->rf_ev, hipEventDisableTiming));
-  if (host_arrays) {
-    HIP_TRY(c->rf_in.ensure(stage));
-    if (c->rf_pin_bytes < stage) {
-      if (c->rf_pin_used) HIP_TRY(hipEventSynchronize(c->rf_ev));
-      c->rf_pin_used = false;
-      if (c->rf_pin) HIP_TRY(hipHostFree(c->rf_pin));
-      c->rf_pin = nullptr;
-      c->rf_pin_bytes = 0;
-      HIP_TRY(hipHostMalloc(&c->rf_pin, stage, hipHostMallocDefault));
-      c->rf_pin_bytes = stage;
-    }
-  }
-  return PRT_OK;
-}
-
-// The tree levels of mesh mi, once: its nodes are read back, every link is checked (an interior child after its
-// parent and inside the mesh's nodes, a leaf slot's records inside the mesh's records), and the nodes ordered by
-// level go to the mesh's part of rf_order.  The node pass then runs one launch per level, deepest first.
-int refit_levels(prt_ctx* c, int32_t mi) {
-  MeshHost& mh = c->mesh_info[mi];
-  if (!mh.level_ends.empty()) return PRT_OK;
-  const uint32_t root = c->mesh_host[mi].root;
-  const size_t n = (size_t)mh.nodes;
-  std::vector<Node8> nd(n);
-  HIP_TRY(hipMemcpyAsync(nd.data(), c->nodes8.as<Node8>() + root, n * sizeof(Node8), hipMemcpyDeviceToHost, c->stream));
-  int rc = wait_stream(c, "reading the mesh's BLAS");
-  if (rc) return rc;
-  std::vector<uint32_t> level(n, 0);
-  uint32_t depth = 1;
-  for (size_t j = 0; j < n; j++) {
-    uint32_t child = nd[j].child_base;
-    for (int s = 0; s < 8; s++) {
-      if ((nd[j].imask >> s) & 1u) {
-        const uint64_t l = (uint64_t)child++ - root;
-        if (child <= root || l <= j || l >= n) return fail(PRT_ERR_HIP, "BLAS refit: an interior child is not below its parent");
-        level[l] = level[j] + 1;
-        depth = std::max(depth, level[l] + 1);
-      } else if (nd[j].meta[s]) {
-        const uint64_t first = (uint64_t)nd[j].tri_base + (nd[j].meta[s] >> 3), cnt = nd[j].meta[s] & 7u;
-        if (first < mh.rec_base || first + cnt > (uint64_t)mh.rec_base + mh.recs)
-          return fail(PRT_ERR_HIP, "BLAS refit: a leaf slot's records lie outside the mesh");
-      }
-    }
-  }
-  std::vector<uint32_t> ends(depth, 0), order(n);
-  for (size_t j = 0; j < n; j++) ends[level[j]]++;
-  uint32_t at = 0;
-  std::vector<uint32_t> next(depth);
-  for (uint32_t d = 0; d < depth; d++) {
-    next[d] = at;
-    at += ends[d];
-    ends[d] = at;
-  }
-  for (size_t j = 0; j < n; j++) order[next[level[j]]++] = root + (uint32_t)j;
-  HIP_TRY(hipMemcpyAsync(c->rf_order.as<uint32_t>() + root, order.data(), n * 4, hipMemcpyHostToDevice, c->stream));
-  rc = wait_stream(c, "uploading the mesh's tree levels");
-  if (rc) return rc;
-  mh.level_ends = std::move(ends);
-  return PRT_OK;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -667,9 +546,9 @@ int prt_destroy(prt_ctx* c) {
   c->tlas_worker.reset();  // every job is done: each one's stream wait ran before the synchronisations above
   for (InstSet& I : c->isets)
     for (auto& u : I.uses) (void)hipEventDestroy(u.second);
-  if (c->rf_ev) (void)hipEventDestroy(c->rf_ev);
-  if (c->rf_pin) (void)hipHostFree(c->rf_pin);
-  if (c->rf_res_host) (void)hipHostFree(c->rf_res_host);
+  if (c->rf.ev) (void)hipEventDestroy(c->rf.ev);
+  if (c->rf.pin) (void)hipHostFree(c->rf.pin);
+  if (c->rf.res_host) (void)hipHostFree(c->rf.res_host);
   if (c->stage_flag) (void)hipHostFree(c->stage_flag);
   for (StageSlot& st : c->stage) {  // the pinned upload ring (its copies ran: the streams are synchronised)
     if (st.ev) (void)hipEventDestroy(st.ev);
@@ -688,8 +567,7 @@ int prt_destroy(prt_ctx* c) {
 
 int prt_set_stream(prt_ctx* c, void* s) {
   if (!c) return fail(PRT_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  const int rc = join_flights(c);  // the frames in flight complete in the old stream's order
-  if (rc) return rc;
+  PRT_TRY(join_flights(c));  // the frames in flight complete in the old stream's order
   c->stream = s ? reinterpret_cast<hipStream_t>(s) : c->own_stream;
   c->ws.pvalid = false;  // the kept primary hits were written in the old stream's order: trace them again in the new
   return PRT_OK;
@@ -736,463 +614,11 @@ int prt_set_textures(prt_ctx* c, const prt_texture* t, int32_t n) {
     host[i].pad = 0;
     all.insert(all.end(), t[i].pixels, t[i].pixels + (size_t)t[i].width * t[i].height);
   }
-  int rc = drain(c);
-  if (rc) return rc;
+  PRT_TRY(drain(c));
   HIP_TRY(upload(c->texels, all.data(), all.size() * 4));
   HIP_TRY(upload(c->tex, host.data(), host.size() * sizeof(TexDev)));
   c->tex_host = host;
   PRT_FOR_MEMBERS(prt_set_textures(m, t, n));
-  return PRT_OK;
-}
-
-int prt_set_meshes(prt_ctx* c, const prt_mesh* m_in, int32_t n) {
-  const prt_mesh* m = m_in;
-  if (!c || !m || n <= 0) return fail(PRT_ERR_INVALID_ARGUMENT, "bad meshes");
-  PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
-  const int builder = c->builder < 0 ? PRT_BUILDER_HOST_SAH : c->builder;
-  const bool gpu = builder == PRT_BUILDER_GPU_LBVH || builder == PRT_BUILDER_GPU_PLOC;
-  int rc = drain(c);
-  if (rc) return rc;
-  const auto t_build0 = std::chrono::steady_clock::now();
-  struct GpuMesh { DevBuf nodes, tris; GpuBlasInfo gi; uint32_t node_base, tri_base, prim_base; };
-  std::vector<GpuMesh> gm(gpu ? n : 0);
-  uint32_t gpu_nodes = 0, gpu_tris = 0;
-  std::vector<Node8> nodes8;
-  std::vector<TriMT> tris;
-  std::vector<ShadeTri> stri;
-  std::vector<MeshDev> mh(n);
-  std::vector<MeshHost> info(n);
-  int maxd = 0;
-  for (int32_t i = 0; i < n; i++) {
-    const prt_mesh& M = m[i];
-    if (M.tri_count <= 0 || M.vertex_count <= 0 || !M.triangles || !M.fixed_normals || !M.fixed_uvs || !M.indices ||
-        !M.vertices || !M.face_normals)
-      return fail(PRT_ERR_INVALID_ARGUMENT, "mesh " + std::to_string(i) + ": missing arrays");
-    const int32_t ntex = (int32_t)c->tex_host.size();
-    if (M.albedo_tex < 0 || M.albedo_tex >= ntex)
-      return fail(PRT_ERR_INVALID_ARGUMENT, "mesh " + std::to_string(i) + ": albedo texture required (Scene.cpp:160)");
-    const int32_t tx[4] = {M.albedo_tex, M.normal_tex, M.metalness_tex, M.emission_tex};
-    const TexDev& A = c->tex_host[M.albedo_tex];
-    for (int k = 1; k < 4; k++) {
-      if (tx[k] >= ntex) return fail(PRT_ERR_INVALID_ARGUMENT, "texture id out of range");
-      // every map is read at the flat texel iu + iv * albedo width, iu and iv taken with the albedo dimensions
-      // (Scene.cpp:79-85,160-165): the map needs that many texels, whatever its own width (a narrower, taller map
-      // renders in the reference and must here)
-      if (tx[k] >= 0 && c->tex_host[tx[k]].w * (int64_t)c->tex_host[tx[k]].h < (int64_t)A.w * A.h)
-        return fail(PRT_ERR_INVALID_ARGUMENT, "texture smaller than the albedo map (indexed with albedo dims)");
-    }
-    for (int64_t k = 0; k < 3 * (int64_t)M.tri_count; k++)
-      if (M.indices[k] < 0 || M.indices[k] >= M.vertex_count) return fail(PRT_ERR_INVALID_ARGUMENT, "index out of range");
-    const uint32_t tri_base = gpu ? gpu_tris : (uint32_t)tris.size();
-    float bmin[3], bmax[3];
-    int depth = 0;
-    int64_t nnodes = 0, nleaves = 0;
-    if (gpu) {  // LBVH or PLOC + SAH-optimal 8-wide collapse on the device (bvh_gpu.hip)
-      GpuMesh& g = gm[i];
-      DevBuf fat;
-      HIP_TRY(upload(fat, M.triangles, 48ull * (size_t)M.tri_count));
-      HIP_TRY(g.nodes.ensure(sizeof(Node8) * (size_t)M.tri_count));
-      HIP_TRY(g.tris.ensure(sizeof(TriMT) * (size_t)M.tri_count));
-      HIP_TRY(gpu_build_blas8(c->stream, fat.as<float>(), M.tri_count, max_leaf_tris(), g.nodes.as<Node8>(), g.tris.as<TriMT>(), &g.gi,
-                              builder == PRT_BUILDER_GPU_PLOC));
-      fat.release();
-      if ((uint64_t)gpu_nodes + g.gi.nodes >= (1ull << 32) || (uint64_t)gpu_tris + g.gi.tris >= (1ull << 32))
-        return fail(PRT_ERR_UNSUPPORTED, "too many triangles");
-      g.node_base = gpu_nodes;
-      g.tri_base = gpu_tris;
-      gpu_nodes += g.gi.nodes;
-      gpu_tris += g.gi.tris;
-      mh[i].root = g.node_base;
-      for (int k = 0; k < 3; k++) { bmin[k] = g.gi.bmin[k]; bmax[k] = g.gi.bmax[k]; }
-      depth = g.gi.depth; nnodes = g.gi.nodes; nleaves = g.gi.leaves;
-    } else {
-      // rebase child / triangle offsets into the concatenated arrays
-      auto append = [&](BuiltBlas8&& built, std::vector<Node8>& all) -> bool {
-        const uint32_t node_base = (uint32_t)all.size();
-        if ((uint64_t)tri_base + built.tris.size() >= (1ull << 32) ||
-            (uint64_t)node_base + built.nodes.size() >= (1ull << 32))
-          return false;
-        for (auto& nd : built.nodes) {
-          nd.child_base += node_base;
-          nd.tri_base += tri_base;
-        }
-        all.insert(all.end(), built.nodes.begin(), built.nodes.end());
-        tris.insert(tris.end(), built.tris.begin(), built.tris.end());
-        mh[i].root = node_base;
-        std::memcpy(bmin, built.bmin, sizeof(bmin));
-        std::memcpy(bmax, built.bmax, sizeof(bmax));
-        depth = built.depth; nnodes = (int64_t)built.nodes.size(); nleaves = built.leaves;
-        return true;
-      };
-      const bool ok = append(build_blas8(M.triangles, M.tri_count, max_leaf_tris(), builder == PRT_BUILDER_HOST_SBVH),
-                             nodes8);
-      if (!ok) return fail(PRT_ERR_UNSUPPORTED, "too many triangles");
-    }
-    mh[i].prim_base = (uint32_t)stri.size();
-    mh[i].vert_base = 0;
-    mh[i].tri_count = (uint32_t)M.tri_count;
-    for (int k = 0; k < 4; k++) mh[i].tex[k] = tx[k];
-    const size_t T = (size_t)M.tri_count;
-    for (size_t p = 0; p < T; p++) {
-      ShadeTri st;
-      std::memset(&st, 0, sizeof(st));
-      for (int k = 0; k < 3; k++) {
-        const size_t c3 = 3 * p + k;
-        const float* vp = M.vertices + 3 * (size_t)M.indices[c3];
-        for (int j = 0; j < 3; j++) {
-          st.n[3 * k + j] = M.fixed_normals[4 * c3 + j];
-          st.p[3 * k + j] = vp[j];
-          st.fn[j] = M.face_normals[3 * p + j];
-        }
-        st.uv[2 * k] = M.fixed_uvs[2 * c3];
-        st.uv[2 * k + 1] = M.fixed_uvs[2 * c3 + 1];
-      }
-      stri.push_back(st);
-    }
-    // ShadeTri.pad[0]: the primitive's TriMT record (the cooperative traversal tail re-tests a helper's
-    // winning triangle from its primitive id, prt_persist.h)
-    if (gpu) gm[i].prim_base = mh[i].prim_base;
-    else
-      for (size_t g = tri_base; g < tris.size(); g++) stri[mh[i].prim_base + tris[g].prim].pad[0] = (uint32_t)g;
-
-    for (int k = 0; k < 3; k++) { info[i].bmin[k] = bmin[k]; info[i].bmax[k] = bmax[k]; }
-    info[i].depth = depth;
-    info[i].nodes = nnodes;
-    info[i].leaves = nleaves;
-    info[i].tris = M.tri_count;
-    info[i].rec_base = tri_base;
-    info[i].recs = gpu ? gm[i].gi.tris : (uint32_t)(tris.size() - tri_base);
-    info[i].verts = M.vertex_count;
-    maxd = std::max(maxd, depth);
-  }
-  c->nodes8.release();
-  if (gpu) {  // concatenate the per-mesh device results, rebase offsets, primitive -> triangle records
-    HIP_TRY(c->nodes8.ensure(sizeof(Node8) * (size_t)gpu_nodes));
-    HIP_TRY(c->tris.ensure(sizeof(TriMT) * (size_t)gpu_tris));
-    HIP_TRY(upload(c->stri, stri.data(), stri.size() * sizeof(ShadeTri)));
-    for (int32_t i = 0; i < n; i++) {
-      GpuMesh& g = gm[i];
-      HIP_TRY(hipMemcpyAsync(c->nodes8.as<Node8>() + g.node_base, g.nodes.p, sizeof(Node8) * (size_t)g.gi.nodes,
-                             hipMemcpyDeviceToDevice, c->stream));
-      HIP_TRY(hipMemcpyAsync(c->tris.as<TriMT>() + g.tri_base, g.tris.p, sizeof(TriMT) * (size_t)g.gi.tris,
-                             hipMemcpyDeviceToDevice, c->stream));
-      HIP_TRY(gpu_blas_finish(c->stream, c->nodes8.as<Node8>() + g.node_base, g.gi.nodes, g.node_base,
-                              c->tris.as<TriMT>() + g.tri_base, g.gi.tris, g.tri_base, c->stri.as<ShadeTri>(),
-                              g.prim_base));
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    gm.clear();  // the per-mesh device builds were copied into the concatenated arrays
-  } else {
-    HIP_TRY(upload(c->nodes8, nodes8.data(), nodes8.size() * sizeof(Node8)));
-    HIP_TRY(upload(c->tris, tris.data(), tris.size() * sizeof(TriMT)));
-    HIP_TRY(upload(c->stri, stri.data(), stri.size() * sizeof(ShadeTri)));
-  }
-  c->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build0).count();
-  c->built_with = builder;
-  HIP_TRY(upload(c->mesh, mh.data(), mh.size() * sizeof(MeshDev)));
-  c->mesh_host = mh;
-  c->mesh_info = info;
-  c->max_depth = maxd;
-  c->snap.clear();  // the snapshots of the previous meshes (prt_snapshot_mesh): nothing queued reads them (drain)
-  c->snap_host.clear();
-  c->snap_tab.release();
-  c->skin.clear();  // the skin bindings of the previous meshes (prt_set_mesh_skin), likewise
-  c->inst_dirty = true;
-  c->tlas_dirty = true;
-  c->scene_epoch++;  // new geometry and BLASes (and prim bits of the hit word): kept primary hits are stale
-  PRT_FOR_MEMBERS(prt_set_meshes(m, m_in, n));
-  return PRT_OK;
-}
-
-int prt_update_mesh(prt_ctx* c, int32_t mi, const prt_mesh* M, uint32_t in_flags) {
-  if (!c || !M) return fail(PRT_ERR_INVALID_ARGUMENT, "bad arguments");
-  if (in_flags & ~PRT_IN_DEVICE) return fail(PRT_ERR_INVALID_ARGUMENT, "unknown input flags");
-  if (c->mesh_host.empty()) return fail(PRT_ERR_NOT_READY, "no meshes: call prt_set_meshes");
-  if (mi < 0 || (size_t)mi >= c->mesh_host.size()) return fail(PRT_ERR_INVALID_ARGUMENT, "mesh index out of range");
-  const bool dev_in = (in_flags & PRT_IN_DEVICE) != 0;
-  if (dev_in && c->sh_kind == 2) return fail(PRT_ERR_UNSUPPORTED, "device arrays on a local shard group");
-  if (!M->triangles || !M->fixed_normals || !M->fixed_uvs || !M->indices || !M->vertices || !M->face_normals)
-    return fail(PRT_ERR_INVALID_ARGUMENT, "mesh update: missing arrays");
-  const MeshDev& md = c->mesh_host[mi];
-  {
-    const MeshHost& mh = c->mesh_info[mi];
-    const int32_t tx[4] = {M->albedo_tex, M->normal_tex, M->metalness_tex, M->emission_tex};
-    if (M->tri_count != mh.tris || M->vertex_count != mh.verts)
-      return fail(PRT_ERR_INVALID_ARGUMENT, "mesh update: the triangle and vertex counts must stay (topology changes need prt_set_meshes)");
-    for (int k = 0; k < 4; k++)
-      if (tx[k] != md.tex[k]) return fail(PRT_ERR_INVALID_ARGUMENT, "mesh update: the texture ids must stay");
-  }
-  const size_t T = (size_t)M->tri_count, V = (size_t)M->vertex_count;
-  if (!dev_in)
-    for (size_t k = 0; k < 3 * T; k++)
-      if (M->indices[k] < 0 || M->indices[k] >= M->vertex_count) return fail(PRT_ERR_INVALID_ARGUMENT, "index out of range");
-  PRT_JOIN(c);  // frames in flight complete first: they read the geometry this call rewrites in place
-  HIP_TRY(hipSetDevice(c->device));
-  int rc = refit_scratch(c, !dev_in);
-  if (rc) return rc;
-  rc = refit_levels(c, mi);
-  if (rc) return rc;
-  MeshHost& mh = c->mesh_info[mi];
-  RefitMeshDev d;
-  d.tri_count = M->tri_count;
-  d.vertex_count = M->vertex_count;
-  const void* src[6] = {M->triangles, M->fixed_normals, M->fixed_uvs, M->indices, M->vertices, M->face_normals};
-  if (!dev_in) {  // through the context's pinned buffer, one copy
-    const RefitStage st = refit_stage(T, V);
-    if (c->rf_pin_used) HIP_TRY(hipEventSynchronize(c->rf_ev));  // the previous update's copy out of it has run
-    c->rf_pin_used = false;
-    char* pin = static_cast<char*>(c->rf_pin);
-    for (int k = 0; k < 6; k++) std::memcpy(pin + st.off[k], src[k], st.bytes[k]);
-    HIP_TRY(hipMemcpyAsync(c->rf_in.p, pin, st.total, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipEventRecord(c->rf_ev, c->stream));
-    c->rf_pin_used = true;
-    for (int k = 0; k < 6; k++) src[k] = c->rf_in.as<char>() + st.off[k];
-  }
-  d.triangles = static_cast<const float*>(src[0]);
-  d.fixed_normals = static_cast<const float*>(src[1]);
-  d.fixed_uvs = static_cast<const float*>(src[2]);
-  d.indices = static_cast<const int32_t*>(src[3]);
-  d.vertices = static_cast<const float*>(src[4]);
-  d.face_normals = static_cast<const float*>(src[5]);
-  RefitResult* res = c->rf_res.as<RefitResult>();
-  HIP_TRY(hipMemsetAsync(&res->bad_index, 0, 4, c->stream));
-  HIP_TRY(launch_refit_records(c->stream, c->tris.as<TriMT>() + mh.rec_base, mh.recs, c->stri.as<ShadeTri>() + md.prim_base, d,
-                               res));
-  for (size_t lv = mh.level_ends.size(); lv-- > 0;) {  // deepest level first; the root last
-    const uint32_t b = lv ? mh.level_ends[lv - 1] : 0u;
-    HIP_TRY(launch_refit_level(c->stream, c->nodes8.as<Node8>(), c->tris.as<TriMT>(), d.triangles, c->rf_box.as<float>(),
-                               c->rf_order.as<uint32_t>() + md.root + b, mh.level_ends[lv] - b, md.root, res));
-  }
-  // the mesh's new box, which the instance records and the instance BVH (built on the host) start from
-  float bmin[3], bmax[3];
-  bool bad = false;
-  if (dev_in) {  // the root box and the bad-index flag, 28 bytes: the call's only host wait
-    HIP_TRY(hipMemcpyAsync(c->rf_res_host, res, sizeof(RefitResult), hipMemcpyDeviceToHost, c->stream));
-    rc = wait_stream(c, "reading the updated mesh's box");
-    if (rc) return rc;
-    std::memcpy(bmin, c->rf_res_host->bmin, sizeof(bmin));
-    std::memcpy(bmax, c->rf_res_host->bmax, sizeof(bmax));
-    bad = c->rf_res_host->bad_index != 0;
-  } else {
-    refit_box_reset(bmin, bmax);
-    for (size_t p = 0; p < T; p++) {
-      const float* a = M->triangles + 12 * p;
-      float lo[3], hi[3];
-      refit_box_reset(lo, hi);
-      refit_box_grow(lo, hi, a);
-      refit_box_grow(lo, hi, a + 4);
-      refit_box_grow(lo, hi, a + 8);
-      refit_box_merge(bmin, bmax, lo, hi);
-    }
-  }
-  std::memcpy(mh.bmin, bmin, sizeof(bmin));
-  std::memcpy(mh.bmax, bmax, sizeof(bmax));
-  c->inst_dirty = true;
-  c->tlas_dirty = true;
-  c->scene_epoch++;  // new geometry: kept primary hits and light visibility are stale
-  if (bad) return fail(PRT_ERR_INVALID_ARGUMENT, "mesh update: an index in device memory is out of range (vertex 0 was read in its place)");
-  PRT_FOR_MEMBERS(prt_update_mesh(m, mi, M, in_flags));
-  return PRT_OK;
-}
-
-int prt_snapshot_mesh(prt_ctx* c, int32_t mi) {
-  if (!c) return fail(PRT_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  if (c->mesh_host.empty()) return fail(PRT_ERR_NOT_READY, "no meshes: call prt_set_meshes");
-  if (mi < 0 || (size_t)mi >= c->mesh_host.size()) return fail(PRT_ERR_INVALID_ARGUMENT, "mesh index out of range");
-  PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t nmesh = c->mesh_host.size();
-  const MeshDev& md = c->mesh_host[mi];
-  if (c->snap.size() != nmesh) {  // the context's first snapshot of these meshes: the table, no snapshot anywhere
-    c->snap.clear();
-    c->snap.resize(nmesh);
-    c->snap_host.assign(nmesh, nullptr);
-    HIP_TRY(c->snap_tab.ensure(nmesh * sizeof(const float*)));
-    HIP_TRY(hipMemsetAsync(c->snap_tab.p, 0, nmesh * sizeof(const float*), c->stream));
-  }
-  if (!c->snap[mi].p) {  // the mesh's first snapshot: its storage, and its entry in the table (the one host wait)
-    HIP_TRY(c->snap[mi].ensure(36 * (size_t)md.tri_count));
-    c->snap_host[mi] = c->snap[mi].as<const float>();
-    const int rc = wait_stream(c, "prt_snapshot_mesh");
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(c->snap_tab.as<const float*>() + mi, &c->snap_host[mi], sizeof(const float*),
-                      hipMemcpyHostToDevice));
-  }
-  HIP_TRY(launch_snapshot_mesh(c->stream, c->stri.as<ShadeTri>() + md.prim_base, md.tri_count,
-                               c->snap[mi].as<float>()));
-  PRT_FOR_MEMBERS(prt_snapshot_mesh(m, mi));
-  return PRT_OK;
-}
-
-int prt_set_mesh_skin(prt_ctx* c, int32_t mi, const prt_skin* S) {
-  if (!c) return fail(PRT_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  if (c->mesh_host.empty()) return fail(PRT_ERR_NOT_READY, "no meshes: call prt_set_meshes");
-  if (mi < 0 || (size_t)mi >= c->mesh_host.size()) return fail(PRT_ERR_INVALID_ARGUMENT, "mesh index out of range");
-  if (S) {  // every check on the host, before anything changes
-    const MeshHost& mh = c->mesh_info[mi];
-    if (S->vertex_count != mh.verts || S->tri_count != mh.tris)
-      return fail(PRT_ERR_INVALID_ARGUMENT, "mesh skin: the vertex and triangle counts must equal the mesh's");
-    if (S->joint_count < 1 || S->joint_count > 65536)
-      return fail(PRT_ERR_INVALID_ARGUMENT, "mesh skin: joint_count must be 1..65536");
-    if (!S->positions || !S->normals || !S->indices || !S->joints || !S->weights)
-      return fail(PRT_ERR_INVALID_ARGUMENT, "mesh skin: missing arrays");
-    for (size_t k = 0; k < 3 * (size_t)S->tri_count; k++)
-      if (S->indices[k] < 0 || S->indices[k] >= S->vertex_count) return fail(PRT_ERR_INVALID_ARGUMENT, "mesh skin: index out of range");
-    for (size_t k = 0; k < 4 * (size_t)S->vertex_count; k++)
-      if ((int32_t)S->joints[k] >= S->joint_count) return fail(PRT_ERR_INVALID_ARGUMENT, "mesh skin: joint out of range");
-  }
-  PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
-  HIP_TRY(hipSetDevice(c->device));
-  // an earlier prt_skin_mesh's kernels may still read the binding this call replaces or removes
-  int rc = wait_stream(c, "prt_set_mesh_skin");
-  if (rc) return rc;
-  if (c->skin.size() != c->mesh_host.size()) {
-    c->skin.clear();
-    c->skin.resize(c->mesh_host.size());
-  }
-  SkinBinding& b = c->skin[mi];
-  b.joints = 0;
-  if (!S) {
-    b = SkinBinding();
-    PRT_FOR_MEMBERS(prt_set_mesh_skin(m, mi, S));
-    return PRT_OK;
-  }
-  const size_t V = (size_t)S->vertex_count, T = (size_t)S->tri_count, J = (size_t)S->joint_count;
-  const void* src[5] = {S->positions, S->normals, S->joints, S->weights, S->indices};
-  const size_t bytes[5] = {12 * V, 12 * V, 8 * V, 16 * V, 12 * T};
-  size_t off[5], at = 0;
-  for (int k = 0; k < 5; k++) {
-    off[k] = at;
-    at += (bytes[k] + 255) & ~size_t(255);
-  }
-  HIP_TRY(b.in.ensure(at));
-  HIP_TRY(b.mats.ensure(48 * J));
-  HIP_TRY(b.work.ensure(32 * V + 48 * T));
-  for (int k = 0; k < 5; k++)
-    if (bytes[k]) HIP_TRY(hipMemcpy(b.in.as<char>() + off[k], src[k], bytes[k], hipMemcpyHostToDevice));
-  SkinDev& d = b.dev;
-  d.positions = reinterpret_cast<const float*>(b.in.as<char>() + off[0]);
-  d.normals = reinterpret_cast<const float*>(b.in.as<char>() + off[1]);
-  d.joints = reinterpret_cast<const uint2*>(b.in.as<char>() + off[2]);
-  d.weights = reinterpret_cast<const float4*>(b.in.as<char>() + off[3]);
-  d.indices = reinterpret_cast<const int32_t*>(b.in.as<char>() + off[4]);
-  d.matrices = b.mats.as<const float4>();
-  d.vpos = b.work.as<float4>();
-  d.vnrm = d.vpos + V;
-  d.triangles = d.vnrm + V;
-  d.vertex_count = S->vertex_count;
-  d.tri_count = S->tri_count;
-  d.joint_count = S->joint_count;
-  b.joints = S->joint_count;
-  PRT_FOR_MEMBERS(prt_set_mesh_skin(m, mi, S));
-  return PRT_OK;
-}
-
-int prt_skin_mesh(prt_ctx* c, int32_t mi, const float* M, int32_t J, uint32_t in_flags) {
-  if (!c) return fail(PRT_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  if (in_flags & ~PRT_IN_DEVICE) return fail(PRT_ERR_INVALID_ARGUMENT, "unknown input flags");
-  if (c->mesh_host.empty()) return fail(PRT_ERR_NOT_READY, "no meshes: call prt_set_meshes");
-  if (mi < 0 || (size_t)mi >= c->mesh_host.size()) return fail(PRT_ERR_INVALID_ARGUMENT, "mesh index out of range");
-  const bool dev_in = (in_flags & PRT_IN_DEVICE) != 0;
-  if (dev_in && c->sh_kind == 2) return fail(PRT_ERR_UNSUPPORTED, "device matrices on a local shard group");
-  if (c->skin.size() != c->mesh_host.size() || !c->skin[mi].joints)
-    return fail(PRT_ERR_NOT_READY, "no skin bound to the mesh: call prt_set_mesh_skin");
-  SkinBinding& b = c->skin[mi];
-  if (!M) return fail(PRT_ERR_INVALID_ARGUMENT, "joint_matrices is NULL");
-  if (J != b.joints) return fail(PRT_ERR_INVALID_ARGUMENT, "joint_count differs from the binding's");
-  if (dev_in && (reinterpret_cast<uintptr_t>(M) & 15u))
-    return fail(PRT_ERR_INVALID_ARGUMENT, "device joint matrices must be 16-byte aligned");
-  PRT_JOIN(c);  // frames in flight complete first: they read the geometry this call rewrites in place
-  HIP_TRY(hipSetDevice(c->device));
-  int rc = refit_scratch(c, false);
-  if (rc) return rc;
-  rc = refit_levels(c, mi);
-  if (rc) return rc;
-  const MeshDev& md = c->mesh_host[mi];
-  MeshHost& mh = c->mesh_info[mi];
-  SkinDev d = b.dev;
-  if (dev_in) {
-    d.matrices = reinterpret_cast<const float4*>(M);
-  } else {  // copied into a pinned staging buffer now, uploaded in stream order
-    StageSlot* st = nullptr;
-    PRT_TRY(stage_acquire(c, 48 * (size_t)J, st));
-    std::memcpy(st->p, M, 48 * (size_t)J);
-    HIP_TRY(hipMemcpyAsync(b.mats.p, st->p, 48 * (size_t)J, hipMemcpyHostToDevice, c->stream));
-    PRT_TRY(stage_release(c, *st, c->stream));
-  }
-  HIP_TRY(launch_skin_mesh(c->stream, d, c->stri.as<ShadeTri>() + md.prim_base));
-  // the refit over the scratch's fat triangles: the record pass without its ShadeTri kernel (tri_count 0: k_skin_prims
-  // wrote those words), then the node levels
-  RefitResult* res = c->rf_res.as<RefitResult>();
-  RefitMeshDev r = {};
-  r.triangles = reinterpret_cast<const float*>(d.triangles);
-  HIP_TRY(launch_refit_records(c->stream, c->tris.as<TriMT>() + mh.rec_base, mh.recs, nullptr, r, res));
-  for (size_t lv = mh.level_ends.size(); lv-- > 0;) {  // deepest level first; the root last
-    const uint32_t lb = lv ? mh.level_ends[lv - 1] : 0u;
-    HIP_TRY(launch_refit_level(c->stream, c->nodes8.as<Node8>(), c->tris.as<TriMT>(), r.triangles, c->rf_box.as<float>(),
-                               c->rf_order.as<uint32_t>() + md.root + lb, mh.level_ends[lv] - lb, md.root, res));
-  }
-  // the mesh's new root box (24 of the result's 28 bytes): the call's only host wait
-  HIP_TRY(hipMemcpyAsync(c->rf_res_host, res, sizeof(RefitResult), hipMemcpyDeviceToHost, c->stream));
-  rc = wait_stream(c, "reading the skinned mesh's box");
-  if (rc) return rc;
-  std::memcpy(mh.bmin, c->rf_res_host->bmin, sizeof(mh.bmin));
-  std::memcpy(mh.bmax, c->rf_res_host->bmax, sizeof(mh.bmax));
-  c->inst_dirty = true;
-  c->tlas_dirty = true;
-  c->scene_epoch++;  // new geometry: kept primary hits and light visibility are stale
-  PRT_FOR_MEMBERS(prt_skin_mesh(m, mi, M, J, in_flags));
-  return PRT_OK;
-}
-
-int prt_read_blas(prt_ctx* c, int32_t mi, void* nodes, uint64_t bytes, uint64_t* needed) {
-  if (!c) return fail(PRT_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  if (c->mesh_host.empty()) return fail(PRT_ERR_NOT_READY, "no meshes: call prt_set_meshes");
-  if (mi < 0 || (size_t)mi >= c->mesh_host.size()) return fail(PRT_ERR_INVALID_ARGUMENT, "mesh index out of range");
-  const MeshHost& mh = c->mesh_info[mi];
-  const uint64_t need = (uint64_t)mh.nodes * sizeof(Node8);
-  if (needed) *needed = need;
-  if (!nodes) return PRT_OK;
-  if (bytes < need) return fail(PRT_ERR_INVALID_ARGUMENT, "prt_read_blas: buffer too small");
-  PRT_JOIN(c);
-  HIP_TRY(hipSetDevice(c->device));
-  const uint32_t root = c->mesh_host[mi].root;
-  HIP_TRY(hipMemcpyAsync(nodes, c->nodes8.as<Node8>() + root, need, hipMemcpyDeviceToHost, c->stream));
-  const int rc = wait_stream(c, "prt_read_blas");
-  if (rc) return rc;
-  Node8* nd = static_cast<Node8*>(nodes);  // offsets relative to the mesh, as the builders return them
-  for (int64_t j = 0; j < mh.nodes; j++) {
-    Node8 x;
-    std::memcpy(&x, nd + j, sizeof(x));
-    x.child_base -= root;
-    x.tri_base -= mh.rec_base;
-    std::memcpy(nd + j, &x, sizeof(x));
-  }
-  return PRT_OK;
-}
-
-int prt_read_blas_tris(prt_ctx* c, int32_t mi, void* tris, uint64_t bytes, uint64_t* needed) {
-  if (!c) return fail(PRT_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  if (c->mesh_host.empty()) return fail(PRT_ERR_NOT_READY, "no meshes: call prt_set_meshes");
-  if (mi < 0 || (size_t)mi >= c->mesh_host.size()) return fail(PRT_ERR_INVALID_ARGUMENT, "mesh index out of range");
-  const MeshHost& mh = c->mesh_info[mi];
-  const uint64_t need = (uint64_t)mh.recs * sizeof(TriMT);
-  if (needed) *needed = need;
-  if (!tris) return PRT_OK;
-  if (bytes < need) return fail(PRT_ERR_INVALID_ARGUMENT, "prt_read_blas_tris: buffer too small");
-  PRT_JOIN(c);
-  HIP_TRY(hipSetDevice(c->device));
-  // (prim is mesh-local in the device array too: nothing to make relative)
-  HIP_TRY(hipMemcpyAsync(tris, c->tris.as<TriMT>() + mh.rec_base, need, hipMemcpyDeviceToHost, c->stream));
-  return wait_stream(c, "prt_read_blas_tris");
-}
-
-int prt_set_bvh_builder(prt_ctx* c, int32_t builder) {
-  if (!c || builder < PRT_BUILDER_HOST_SAH || builder > PRT_BUILDER_GPU_PLOC)
-    return fail(PRT_ERR_INVALID_ARGUMENT, "bad BLAS builder");
-  c->builder = builder;
-  c->scene_epoch++;  // (the BLASes change at the next prt_set_meshes, which bumps it again)
-  PRT_FOR_MEMBERS(prt_set_bvh_builder(m, builder));
   return PRT_OK;
 }
 
@@ -1208,8 +634,7 @@ int prt_set_instances(prt_ctx* c, const float* xf, const uint32_t* mi, int32_t n
   c->inst_epoch++;  // transforms, boxes, the instance BVH and the hit word's instance bits: kept primary hits are stale
   HIP_TRY(hipSetDevice(c->device));
   if (!c->mesh_host.empty()) {
-    const int rc = ensure_instances(c);
-    if (rc) return rc;
+    PRT_TRY(ensure_instances(c));
   }
   PRT_FOR_MEMBERS(prt_set_instances(m, xf, mi, n));
   return PRT_OK;
@@ -1232,8 +657,7 @@ int prt_set_instance_materials(prt_ctx* c, const int32_t* kinds, int32_t n) {
   c->inst_dirty = true;
   HIP_TRY(hipSetDevice(c->device));
   if (!c->mesh_host.empty() && !c->inst_mesh.empty()) {
-    const int rc = ensure_instances(c);
-    if (rc) return rc;
+    PRT_TRY(ensure_instances(c));
   }
   PRT_FOR_MEMBERS(prt_set_instance_materials(m, kinds, n));
   return PRT_OK;
@@ -1274,8 +698,7 @@ int prt_set_lights(prt_ctx* c, const prt_lights* l) {
 int prt_set_sky(prt_ctx* c, const float* rgb, int32_t w, int32_t h) {
   if (!c) return fail(PRT_ERR_INVALID_ARGUMENT, "ctx is NULL");
   PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
-  int rc = drain(c);
-  if (rc) return rc;
+  PRT_TRY(drain(c));
   if (!rgb || w <= 0 || h <= 0) {
     c->skyw = c->skyh = 0;
     PRT_FOR_MEMBERS(prt_set_sky(m, rgb, w, h));
@@ -1359,14 +782,12 @@ int prt_trace_primary(prt_ctx* c, int32_t W, int32_t H, prt_hit* hits, uint32_t 
   PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
   HIP_TRY(hipSetDevice(c->device));
   SceneDev S;
-  int rc = scene_ready(c, S);
-  if (rc) return rc;
+  PRT_TRY(scene_ready(c, S));
   if (!c->have_camera) return fail(PRT_ERR_NOT_READY, "no camera");
   if (!depth_ok(c)) return fail(PRT_ERR_UNSUPPORTED, "BVH deeper than 64 levels");
   const TileMap M = make_tilemap(W, H, 8, 0, 1);
   const size_t n = (size_t)W * H;
-  rc = ensure_spill(c, S, (size_t)M.items + 256);
-  if (rc) return rc;
+  PRT_TRY(ensure_spill(c, S, (size_t)M.items + 256));
   HitOut* out = reinterpret_cast<HitOut*>(hits);
   Staging io(c, out_flags);
   PRT_TRY(io.out(c->hits, out, n * sizeof(HitOut)));
@@ -1402,11 +823,9 @@ static int ray_query(prt_ctx* c, int32_t n, const float* O, const float* D, cons
   if (n == 0) return PRT_OK;
   HIP_TRY(hipSetDevice(c->device));
   SceneDev S;
-  int rc = scene_ready(c, S);
-  if (rc) return rc;
+  PRT_TRY(scene_ready(c, S));
   if (!depth_ok(c)) return fail(PRT_ERR_UNSUPPORTED, "BVH deeper than 64 levels");
-  rc = ensure_spill(c, S, (size_t)n + 256);
-  if (rc) return rc;
+  PRT_TRY(ensure_spill(c, S, (size_t)n + 256));
   DevBuf dO, dD, dT, dOut;
   auto cleanup = [&]() { dO.release(); dD.release(); dT.release(); dOut.release(); };
   const size_t outb = (size_t)n * (any ? 4 : sizeof(HitOut));
@@ -1443,15 +862,13 @@ int render_aov(prt_ctx* c, int32_t W, int32_t H, uint32_t flags, float* albedo, 
   PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
   HIP_TRY(hipSetDevice(c->device));
   SceneDev S;
-  int rc = scene_ready(c, S);
-  if (rc) return rc;
+  PRT_TRY(scene_ready(c, S));
   if (!c->have_camera) return fail(PRT_ERR_NOT_READY, "no camera");
   if (!depth_ok(c)) return fail(PRT_ERR_UNSUPPORTED, "BVH deeper than 64 levels");
   if (!albedo && !normal_depth && !instance && !offset) return PRT_OK;
   const TileMap M = make_tilemap(W, H, 8, 0, 1);
   const size_t n = (size_t)W * H;
-  rc = ensure_spill(c, S, (size_t)M.items + 256);
-  if (rc) return rc;
+  PRT_TRY(ensure_spill(c, S, (size_t)M.items + 256));
   const bool timed = (out_flags & PRT_OUT_TIMED) != 0;
   HIP_TRY(c->aov_hits.ensure(n * sizeof(HitOut)));
   HIP_TRY(c->counters.ensure(sizeof(Counters)));  // the launch's own ray count: not the running totals
@@ -1465,7 +882,7 @@ int render_aov(prt_ctx* c, int32_t W, int32_t H, uint32_t flags, float* albedo, 
   PRT_TRY(io.out(c->aov_ids, ids, n * 4));
   PRT_TRY(io.out(c->aov_off, off, n * sizeof(float4)));
   LaunchCfg L{c->stream, occ_for(c)};
-  if (timed && (rc = dn_event(c, 0))) return rc;
+  if (timed) PRT_TRY(dn_event(c, 0));
   HIP_TRY(launch_primary_hits(L, S, M, c->aov_hits.as<HitOut>(), c->counters.as<Counters>()));
   if (a || g)
     HIP_TRY(launch_aov(c->stream, S, W, H, (flags & PRT_FLAG_NORMALMAP) != 0, c->aov_hits.as<HitOut>(), a, g));
@@ -1474,7 +891,7 @@ int render_aov(prt_ctx* c, int32_t W, int32_t H, uint32_t flags, float* albedo, 
     HIP_TRY(launch_aov_deform(c->stream, S, W, H, c->aov_hits.as<HitOut>(),
                               c->snap.empty() ? nullptr : c->snap_tab.as<const float*>(), off));
   if (timed) {
-    if ((rc = dn_event(c, 1))) return rc;
+    PRT_TRY(dn_event(c, 1));
     c->dn_timed_aov = 1;
   }
   return io.finish();
@@ -1527,8 +944,7 @@ int prt_shard_init_rccl(prt_ctx* c, const uint8_t id[PRT_SHARD_ID_BYTES], int32_
   if (!c || !id || world <= 0 || rank < 0 || rank >= world) return fail(PRT_ERR_INVALID_ARGUMENT, "bad shard rank / world");
   PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
   if (c->sh_kind != 0) return fail(PRT_ERR_INVALID_ARGUMENT, "context is already sharded");
-  int rc = shard_setup(c, tile);
-  if (rc) return rc;
+  PRT_TRY(shard_setup(c, tile));
   const char* why = nullptr;
   const Rccl* R = rccl(&why);
   if (!R) return fail(PRT_ERR_UNSUPPORTED, why);
@@ -1563,8 +979,7 @@ int prt_shard_attach_rccl(prt_ctx* c, void* comm, int32_t tile) {
   if (!c || !comm) return fail(PRT_ERR_INVALID_ARGUMENT, "ctx / comm is NULL");
   PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
   if (c->sh_kind != 0) return fail(PRT_ERR_INVALID_ARGUMENT, "context is already sharded");
-  int rc = shard_setup(c, tile);
-  if (rc) return rc;
+  PRT_TRY(shard_setup(c, tile));
   const char* why = nullptr;
   const Rccl* R = rccl(&why);
   if (!R) return fail(PRT_ERR_UNSUPPORTED, why);
@@ -1585,9 +1000,8 @@ int prt_create_group(const prt_device_desc* devs, int32_t n, int32_t tile, prt_c
   *out = nullptr;
   if (!devs || n <= 0 || n > 64) return fail(PRT_ERR_INVALID_ARGUMENT, "1..64 devices");
   prt_ctx* g = nullptr;
-  int rc = prt_create(&devs[0], &g);
-  if (rc) return rc;
-  rc = shard_setup(g, tile);
+  PRT_TRY(prt_create(&devs[0], &g));
+  int rc = shard_setup(g, tile);
   for (int32_t k = 1; k < n && !rc; k++) {
     prt_ctx* m = nullptr;
     rc = prt_create(&devs[k], &m);

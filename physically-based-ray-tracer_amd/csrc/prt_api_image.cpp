@@ -363,7 +363,8 @@ int prt_reproject_moments(prt_ctx* c, const prt_temporal_params* p, int32_t W, i
                            motion, count, history_mom, nullptr, nullptr, out_rgba, out_mom, out_rgb8, out_flags);
 }
 
-// ---- deforming meshes in the reprojection (prt_deform.hip; prt_snapshot_mesh and prt_render_aov_deform: prt_api.cpp)
+// ---- deforming meshes in the reprojection (prt_deform.hip; prt_snapshot_mesh: prt_api_mesh.cpp, prt_render_aov_deform:
+// prt_api.cpp)
 int prt_reproject_deform(prt_ctx* c, const prt_temporal_params* p, int32_t W, int32_t H, const prt_camera* cam,
                          const float* color, const float* normal_depth, const uint32_t* instance,
                          const prt_camera* prev_cam, const float* history, const float* history_nd,

@@ -1,6 +1,7 @@
 // prt_api_render.cpp -- the render path of the C ABI (include/prt.h): a call's plan (prt_plan.h), its wavefront
 // state, the enqueue of its passes, frames in flight, stats and the sharded frame; prt_render, prt_render_tiles,
-// prt_untile, the ray-total readers and the accumulation checkpoints.  The scene side is prt_api.cpp.
+// prt_untile, the ray-total readers and the accumulation checkpoints.  The scene side is prt_api.cpp,
+// its meshes prt_api_mesh.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

@@ -160,10 +160,27 @@ struct MeshHost {
   // prt_update_mesh: the mesh's TriMT records [rec_base, rec_base + recs) (more than tris after spatial splits; its
   // nodes are [MeshDev::root, + nodes)), its vertex count, and the tree levels of the node pass (empty until the
   // mesh's first update): level d's nodes are order[level_ends[d - 1] .. level_ends[d]) of the mesh's part of
-  // prt_ctx::rf_order
+  // prt_ctx::rf.order
   uint32_t rec_base = 0, recs = 0;
   int32_t verts = 0;
   std::vector<uint32_t> level_ends;
+};
+
+// The scratch of the refit (prt_update_mesh / prt_skin_mesh, prt_blas_refit.h; prt_ctx::rf), allocated at a context's
+// first update for the scene as it stands and kept: six floats per node (the uninflated boxes), the nodes of every
+// refitted mesh ordered by tree level, the 28-byte result (root box, bad-index flag) and its pinned host copy; for
+// host arrays, the six arrays back to back in one pinned buffer (written again once ev says the previous update's
+// copy has run) and their device copy
+struct RefitScratch {
+  DevBuf box, order, res, in;
+  RefitResult* res_host = nullptr;
+  // One dedicated buffer, not a slot of the prt_ctx::stage ring: at C4 it is 143 MiB, and stage_acquire hands out the
+  // first free slot and grows it on demand, which would pin up to kStageSlots such buffers and put hipHostMalloc
+  // (20-190 ms, profiles/r06_tlas_drift.txt) back into the update path
+  void* pin = nullptr;
+  size_t pin_bytes = 0;
+  hipEvent_t ev = nullptr;
+  bool pin_used = false;
 };
 
 }  // namespace prt::host
@@ -209,16 +226,7 @@ struct prt_ctx {
   size_t stage_bytes = 0;  // the size the pool was last allocated for
   uint32_t* stage_flag = nullptr;      // one coherent pinned word per staging buffer (64-B stride): TlasJob::flag
   uint32_t* stage_flag_dev = nullptr;  // its device address
-  // prt_update_mesh (prt_blas_refit.h), allocated at a context's first update for the scene as it stands and kept:
-  // six floats per node (the uninflated boxes), the nodes of every refitted mesh ordered by tree level, the 28-byte
-  // result (root box, bad-index flag) and its pinned host copy; for host arrays, the six arrays back to back in one
-  // pinned buffer (written again once rf_ev says the previous update's copy has run) and their device copy
-  DevBuf rf_box, rf_order, rf_res, rf_in;
-  prt::RefitResult* rf_res_host = nullptr;
-  void* rf_pin = nullptr;
-  size_t rf_pin_bytes = 0;
-  hipEvent_t rf_ev = nullptr;
-  bool rf_pin_used = false;
+  prt::host::RefitScratch rf;  // prt_update_mesh / prt_skin_mesh
   DevBuf spill;  // traversal stack levels beyond the LDS ones (BVHs deeper than 17 levels)
   DevBuf diag;   // SceneDev::diag device counters ([0] traversal stack overflows, cumulative per context)
   // area light (prt_set_area_lights): p0, eu, ev, n, Le, area
@@ -318,6 +326,18 @@ int ensure_spill(prt_ctx* c, SceneDev& S, size_t threads);
 int scene_ready(prt_ctx* c, SceneDev& S);
 PostDev post_params(const prt_ctx* c, int32_t W, int32_t H);
 int record_inst_use(prt_ctx* c, hipStream_t st);
+// prt_api.cpp, for the mesh entry points (prt_api_mesh.cpp): wait for the context stream (bounded on an RCCL-sharded
+// context, as drain())
+int wait_stream(prt_ctx* c, const char* what);
+// a setter of a local group applies to every member (member 0 = the group context itself)
+#define PRT_FOR_MEMBERS(call) \
+  for (prt_ctx* m : c->members) PRT_TRY(call)
+// the mesh index of an entry point that needs the meshes set
+inline int mesh_arg(const prt_ctx* c, int32_t mi) {
+  if (c->mesh_host.empty()) return fail(PRT_ERR_NOT_READY, "no meshes: call prt_set_meshes");
+  if (mi < 0 || (size_t)mi >= c->mesh_host.size()) return fail(PRT_ERR_INVALID_ARGUMENT, "mesh index out of range");
+  return PRT_OK;
+}
 // prt_api_render.cpp: the context's traversal stack overflow count (waits for the context stream); a shard's tile size
 // and event
 uint64_t diag_overflows(prt_ctx* c, bool* layout_ok = nullptr, bool* wait_ok = nullptr);

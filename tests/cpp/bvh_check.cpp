@@ -223,7 +223,7 @@ static int check_tree(const std::vector<float>& t, const std::vector<Node8>& nod
   return 0;
 }
 
-constexpr int kMaxLeaf = 3;  // max_leaf_tris() of prt_api.cpp
+constexpr int kMaxLeaf = 3;  // max_leaf_tris() of prt_api_mesh.cpp
 
 static int check_blas(const std::vector<float>& t, bool spatial) {
   const BuiltBlas8 b = build_blas8(t.data(), (int32_t)(t.size() / 12), kMaxLeaf, spatial);
