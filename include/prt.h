@@ -272,6 +272,41 @@ int prt_set_mesh_skin(prt_ctx* ctx, int32_t mesh_index, const prt_skin* skin);
  * No binding on the mesh: PRT_ERR_NOT_READY.  joint_count different from the binding's, NULL matrices, unknown
  * flags, a bad index: PRT_ERR_INVALID_ARGUMENT. */
 int prt_skin_mesh(prt_ctx* ctx, int32_t mesh_index, const float* joint_matrices, int32_t joint_count, uint32_t in_flags);
+/* The SAH cost of mesh mesh_index's BLAS as it stands on the device (additive in ABI 10; DESIGN.md 8 "Rebuild"; the
+ * definition: csrc/prt_blas_cost.h): over all its nodes, the decoded box area of every interior slot plus that of
+ * every leaf slot times its triangle count, divided by the area of the box around the root node's occupied slots; 0
+ * when that area is 0.  Areas are dx*dy + dy*dz + dz*dx of the boxes the traversal decodes, in f64; unoccupied slots
+ * contribute nothing.  A refit keeps a tree's topology, so the cost of a mesh that prt_update_mesh / prt_skin_mesh
+ * carried far from the pose its tree was built for grows; the caller compares it with the cost after the build (or
+ * after the last prt_rebuild_mesh) and decides when to rebuild: the library has no policy of its own.
+ * Two kernels on the context stream, no atomics: two calls on the same tree return the same bits.  The call joins
+ * the frames in flight and waits on the host once, for the 8 bytes of the result; its scratch (one f64 per 256 nodes)
+ * is allocated at the first call and kept.  On a local group or RCCL context it runs on the calling member.
+ * NULL context, NULL cost or an index out of range: PRT_ERR_INVALID_ARGUMENT.  No meshes: PRT_ERR_NOT_READY. */
+int prt_blas_cost(prt_ctx* ctx, int32_t mesh_index, double* cost);
+/* prt_update_mesh with a fresh device build in place of the refit (additive in ABI 10; DESIGN.md 8 "Rebuild").
+ * mesh != NULL: the arguments, the checks, the PRT_IN_DEVICE rule, the bad-index rule and the behaviour on a local
+ * group or RCCL context are prt_update_mesh's.  mesh = NULL: the geometry is the fat triangles the mesh's skin binding
+ * holds from its last prt_skin_mesh (no binding, or no prt_skin_mesh on it yet: PRT_ERR_NOT_READY).
+ * builder: PRT_BUILDER_GPU_LBVH or PRT_BUILDER_GPU_PLOC (with PRT_TRBVH as at prt_set_meshes); the host builders
+ * return PRT_ERR_UNSUPPORTED, any other value PRT_ERR_INVALID_ARGUMENT.  prt_scene_info.builder keeps reporting the
+ * last prt_set_meshes; blas_nodes, blas_leaves and max_depth report the live trees.
+ * The contract: afterwards every query, render and AOV returns, bit for bit, what a fresh context returns after
+ * prt_set_meshes with that mesh replaced (hits do not depend on the builder); prt_read_blas / prt_read_blas_tris
+ * return the new tree, the one a fresh context's build of the mesh alone with the same builder makes; the other
+ * meshes' nodes and records are untouched.
+ * The tree is built into scratch the context keeps (128 bytes per triangle of the largest mesh, sized at the first
+ * rebuild after a prt_set_meshes) and committed only after the build succeeded: a failed build -- or a tree deeper
+ * than 64 levels, PRT_ERR_UNSUPPORTED -- leaves the scene as it was.  A tree with at most as many nodes as the mesh's
+ * region of the node array holds (what prt_set_meshes gave it) is committed in place, without draining or
+ * allocating; a larger one moves the mesh's nodes to the end of a regrown node array (that region's size becomes the
+ * mesh's), which drains the context and reallocates once.  A spatial-split mesh's surplus records go unused.
+ * Ordering: the call joins the frames in flight and blocks the host while the builder synchronises (once per tree
+ * level); frames enqueued before it see the old tree, frames enqueued after it the new one.  Snapshots and skin
+ * bindings are kept; the next prt_update_mesh / prt_skin_mesh of the mesh reads the new nodes back once, as after
+ * prt_set_meshes; kept primary hits and light visibility go stale; the instance boxes and the instance BVH follow at
+ * the next frame. */
+int prt_rebuild_mesh(prt_ctx* ctx, int32_t mesh_index, const prt_mesh* mesh, uint32_t in_flags, int32_t builder);
 /* transforms: 16*count floats, row-major BLASInstance::transform; mesh_index: count.  Above 64 instances the rays
  * walk an instance BVH, rebuilt for every call as the reference's per-frame BVH::Build (a host SAH build): on the
  * calling thread when the instance count changes, otherwise on the context's worker thread, the context stream

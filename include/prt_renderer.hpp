@@ -135,6 +135,16 @@ class Scene {
   // models[index] was deformed in place (same topology): its arrays go to the device and its BLAS is refitted there
   // (prt_update_mesh); the instance boxes and the instance BVH follow at the next frame
   void UpdateModel(prt_ctx* ctx, int32_t index) const {
+    const prt_mesh d = MeshDesc(index);
+    check(prt_update_mesh(ctx, index, &d, 0));
+  }
+  // the same with a fresh device build of the model's BLAS in place of the refit (prt_rebuild_mesh; builder:
+  // PRT_BUILDER_GPU_LBVH or PRT_BUILDER_GPU_PLOC): what brings back the tree quality a long deformation cost
+  void RebuildModel(prt_ctx* ctx, int32_t index, int32_t builder = PRT_BUILDER_GPU_PLOC) const {
+    const prt_mesh d = MeshDesc(index);
+    check(prt_rebuild_mesh(ctx, index, &d, 0, builder));
+  }
+  prt_mesh MeshDesc(int32_t index) const {
     const Model& m = models.at((size_t)index);
     prt_mesh d{};
     d.tri_count = m.TriCount();
@@ -149,7 +159,7 @@ class Scene {
     d.normal_tex = m.normalTexture;
     d.metalness_tex = m.metalnessTexture;
     d.emission_tex = m.emissionTexture;
-    check(prt_update_mesh(ctx, index, &d, 0));
+    return d;
   }
   // GameObject::Synchronise moved an instance: new transforms, TLAS rebuilt (Core/Renderer.cpp:33-41)
   void UploadInstances(prt_ctx* ctx) const {
@@ -319,6 +329,23 @@ class Renderer {
   // the accumulation restarts in full (the accumulated frames, sample counts and distances show the old geometry)
   void ModelChanged(int32_t index) {
     scene.UpdateModel(ctx_, index);
+    check(prt_reset_accumulation(ctx_, 1));
+  }
+
+  // The SAH cost of model index's BLAS as it stands (prt_blas_cost): it grows while ModelChanged / SkinModel refit
+  // the tree away from the pose it was built for.  RebuildModel(index) rebuilds it over scene.models[index] as it is
+  // now; RebuildSkinnedModel(index) over the pose of the last SkinModel.  When to rebuild is the caller's decision.
+  double BlasCost(int32_t index) const {
+    double v = 0.0;
+    check(prt_blas_cost(ctx_, index, &v));
+    return v;
+  }
+  void RebuildModel(int32_t index, int32_t builder = PRT_BUILDER_GPU_PLOC) {
+    scene.RebuildModel(ctx_, index, builder);
+    check(prt_reset_accumulation(ctx_, 1));
+  }
+  void RebuildSkinnedModel(int32_t index, int32_t builder = PRT_BUILDER_GPU_PLOC) {
+    check(prt_rebuild_mesh(ctx_, index, nullptr, 0u, builder));
     check(prt_reset_accumulation(ctx_, 1));
   }
 

@@ -1,6 +1,7 @@
 // prt_api_mesh.cpp -- the mesh entry points of the C ABI (include/prt.h): prt_set_meshes and the BLAS builds, the
-// in-place update and skinning with their one refit (refit_mesh), snapshots, skin bindings, the BLAS read-back.  What
-// they decide without a device is prt_mesh_host.h; the context, instances and queries are prt_api.cpp.
+// in-place update and skinning with their one refit (refit_mesh), the rebuild of one mesh's BLAS and its SAH measure,
+// snapshots, skin bindings, the BLAS read-back.  What they decide without a device is prt_mesh_host.h; the context,
+// instances and queries are prt_api.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -10,6 +11,7 @@
 #include <vector>
 
 #include "bvh_gpu.h"
+#include "prt_blas_cost_gpu.h"
 #include "prt_ctx.h"
 #include "prt_deform.h"
 #include "prt_mesh_host.h"
@@ -35,11 +37,11 @@ RefitStage refit_stage(size_t T, size_t V) {
 // context, so nothing queued reads what a larger allocation replaces) and kept: later updates allocate nothing.
 int refit_scratch(prt_ctx* c, bool host_arrays) {
   RefitScratch& rf = c->rf;
-  size_t nodes = 0, stage = 0;
-  for (const MeshHost& m : c->mesh_info) {
-    nodes += (size_t)m.nodes;
-    stage = std::max(stage, refit_stage((size_t)m.tris, (size_t)m.verts).total);
-  }
+  // box and order are indexed by node position: sized for the node array's length, which is more than the sum of
+  // the live nodes once a rebuilt tree was moved to the array's end (prt_rebuild_mesh)
+  const size_t nodes = (size_t)c->nodes_len;
+  size_t stage = 0;
+  for (const MeshHost& m : c->mesh_info) stage = std::max(stage, refit_stage((size_t)m.tris, (size_t)m.verts).total);
   HIP_TRY(rf.box.ensure(24 * nodes));
   HIP_TRY(rf.order.ensure(4 * nodes));
   HIP_TRY(rf.res.ensure(sizeof(RefitResult)));
@@ -122,6 +124,66 @@ int refit_mesh(prt_ctx* c, int32_t mi, const RefitMeshDev& d, bool shade, const 
   c->inst_dirty = true;
   c->tlas_dirty = true;
   c->scene_epoch++;
+  return PRT_OK;
+}
+
+// What prt_update_mesh and prt_rebuild_mesh check of *M before anything changes (`who` names the call in the
+// message): the arrays, the counts and texture ids against the mesh's, host indices against vertex_count.
+int update_args(prt_ctx* c, int32_t mi, const prt_mesh* M, uint32_t in_flags, const std::string& who = "mesh update") {
+  const bool dev_in = (in_flags & PRT_IN_DEVICE) != 0;
+  if (dev_in && c->sh_kind == 2) return fail(PRT_ERR_UNSUPPORTED, "device arrays on a local shard group");
+  std::string why = check_mesh_arrays(*M, kMeshArrays, who, c->tex_host.data(), 0);
+  if (!why.empty()) return fail(PRT_ERR_INVALID_ARGUMENT, why);
+  if (M->tri_count != c->mesh_info[mi].tris || M->vertex_count != c->mesh_info[mi].verts)
+    return fail(PRT_ERR_INVALID_ARGUMENT, who + ": the triangle and vertex counts must stay (topology changes need prt_set_meshes)");
+  const int32_t tx[4] = {M->albedo_tex, M->normal_tex, M->metalness_tex, M->emission_tex};
+  for (int k = 0; k < 4; k++)
+    if (tx[k] != c->mesh_host[mi].tex[k]) return fail(PRT_ERR_INVALID_ARGUMENT, who + ": the texture ids must stay");
+  if (!dev_in) why = check_mesh_arrays(*M, kMeshIndices, who, c->tex_host.data(), 0);
+  if (!why.empty()) return fail(PRT_ERR_INVALID_ARGUMENT, why);
+  return PRT_OK;
+}
+
+// The six arrays of *M as the kernels read them, into d: device arrays as they are; host arrays through the
+// context's pinned buffer, one copy on the context stream (refit_scratch(c, true) sized both buffers).
+int stage_mesh(prt_ctx* c, const prt_mesh* M, bool dev_in, RefitMeshDev& d) {
+  const void* src[6] = {M->triangles, M->fixed_normals, M->fixed_uvs, M->indices, M->vertices, M->face_normals};
+  if (!dev_in) {
+    RefitScratch& rf = c->rf;
+    const RefitStage st = refit_stage((size_t)M->tri_count, (size_t)M->vertex_count);
+    if (rf.pin_used) HIP_TRY(hipEventSynchronize(rf.ev));  // the previous update's copy out of it has run
+    rf.pin_used = false;
+    char* pin = static_cast<char*>(rf.pin);
+    for (int k = 0; k < 6; k++) std::memcpy(pin + st.off[k], src[k], st.bytes[k]);
+    HIP_TRY(hipMemcpyAsync(rf.in.p, pin, st.total, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipEventRecord(rf.ev, c->stream));
+    rf.pin_used = true;
+    for (int k = 0; k < 6; k++) src[k] = rf.in.as<char>() + st.off[k];
+  }
+  d = {static_cast<const float*>(src[0]), static_cast<const float*>(src[1]), static_cast<const float*>(src[2]),
+       static_cast<const int32_t*>(src[3]), static_cast<const float*>(src[4]), static_cast<const float*>(src[5]),
+       M->tri_count, M->vertex_count};
+  return PRT_OK;
+}
+
+// A larger tree than mesh mi's node region holds: the node array grows by `need` nodes and the mesh's region becomes
+// the new end (the region it leaves stays where it is, unused: no other mesh's nodes move).  The only step of a
+// rebuild that drains and reallocates; the refit scratch, indexed by node position, is dropped with every mesh's tree
+// levels and comes back at the next update.
+int grow_nodes(prt_ctx* c, int32_t mi, uint32_t need) {
+  if (c->nodes_len + need >= (1ull << 32)) return fail(PRT_ERR_UNSUPPORTED, "too many BLAS nodes");
+  PRT_TRY(drain(c));
+  DevBuf grown;
+  HIP_TRY(grown.ensure(sizeof(Node8) * (size_t)(c->nodes_len + need)));
+  HIP_TRY(hipMemcpy(grown.p, c->nodes8.p, sizeof(Node8) * (size_t)c->nodes_len, hipMemcpyDeviceToDevice));
+  c->nodes8 = std::move(grown);
+  c->mesh_host[mi].root = (uint32_t)c->nodes_len;
+  c->mesh_info[mi].node_cap = need;
+  c->nodes_len += need;
+  HIP_TRY(upload(c->mesh, c->mesh_host.data(), c->mesh_host.size() * sizeof(MeshDev)));
+  c->rf.box.release();
+  c->rf.order.release();
+  for (MeshHost& m : c->mesh_info) m.level_ends.clear();
   return PRT_OK;
 }
 
@@ -228,6 +290,8 @@ int prt_set_meshes(prt_ctx* c, const prt_mesh* m_in, int32_t n) {
     info[i].rec_base = tri_base;
     info[i].recs = gpu ? gm[i].gi.tris : (uint32_t)(tris.size() - tri_base);
     info[i].verts = M.vertex_count;
+    info[i].node_cap = nnodes;
+    info[i].rec_cap = info[i].recs;
     maxd = std::max(maxd, depth);
   }
   c->nodes8.release();
@@ -257,6 +321,7 @@ int prt_set_meshes(prt_ctx* c, const prt_mesh* m_in, int32_t n) {
   HIP_TRY(upload(c->mesh, mh.data(), mh.size() * sizeof(MeshDev)));
   c->mesh_host = mh;
   c->mesh_info = info;
+  c->nodes_len = gpu ? (uint64_t)gpu_nodes : (uint64_t)nodes8.size();
   c->max_depth = maxd;
   c->snap.clear();  // the snapshots of the previous meshes (prt_snapshot_mesh): nothing queued reads them (drain)
   c->snap_host.clear();
@@ -273,38 +338,14 @@ int prt_update_mesh(prt_ctx* c, int32_t mi, const prt_mesh* M, uint32_t in_flags
   if (!c || !M) return fail(PRT_ERR_INVALID_ARGUMENT, "bad arguments");
   if (in_flags & ~PRT_IN_DEVICE) return fail(PRT_ERR_INVALID_ARGUMENT, "unknown input flags");
   PRT_TRY(mesh_arg(c, mi));
+  PRT_TRY(update_args(c, mi, M, in_flags));
   const bool dev_in = (in_flags & PRT_IN_DEVICE) != 0;
-  if (dev_in && c->sh_kind == 2) return fail(PRT_ERR_UNSUPPORTED, "device arrays on a local shard group");
-  std::string why = check_mesh_arrays(*M, kMeshArrays, "mesh update", c->tex_host.data(), 0);
-  if (!why.empty()) return fail(PRT_ERR_INVALID_ARGUMENT, why);
-  if (M->tri_count != c->mesh_info[mi].tris || M->vertex_count != c->mesh_info[mi].verts)
-    return fail(PRT_ERR_INVALID_ARGUMENT, "mesh update: the triangle and vertex counts must stay (topology changes need prt_set_meshes)");
-  const int32_t tx[4] = {M->albedo_tex, M->normal_tex, M->metalness_tex, M->emission_tex};
-  for (int k = 0; k < 4; k++)
-    if (tx[k] != c->mesh_host[mi].tex[k]) return fail(PRT_ERR_INVALID_ARGUMENT, "mesh update: the texture ids must stay");
-  if (!dev_in) why = check_mesh_arrays(*M, kMeshIndices, "mesh update", c->tex_host.data(), 0);
-  if (!why.empty()) return fail(PRT_ERR_INVALID_ARGUMENT, why);
   PRT_JOIN(c);  // frames in flight complete first: they read the geometry this call rewrites in place
   HIP_TRY(hipSetDevice(c->device));
   PRT_TRY(refit_scratch(c, !dev_in));
   PRT_TRY(refit_levels(c, mi));
-  const void* src[6] = {M->triangles, M->fixed_normals, M->fixed_uvs, M->indices, M->vertices, M->face_normals};
-  if (!dev_in) {  // through the context's pinned buffer, one copy
-    RefitScratch& rf = c->rf;
-    const RefitStage st = refit_stage((size_t)M->tri_count, (size_t)M->vertex_count);
-    if (rf.pin_used) HIP_TRY(hipEventSynchronize(rf.ev));  // the previous update's copy out of it has run
-    rf.pin_used = false;
-    char* pin = static_cast<char*>(rf.pin);
-    for (int k = 0; k < 6; k++) std::memcpy(pin + st.off[k], src[k], st.bytes[k]);
-    HIP_TRY(hipMemcpyAsync(rf.in.p, pin, st.total, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipEventRecord(rf.ev, c->stream));
-    rf.pin_used = true;
-    for (int k = 0; k < 6; k++) src[k] = rf.in.as<char>() + st.off[k];
-  }
-  const RefitMeshDev d = {static_cast<const float*>(src[0]), static_cast<const float*>(src[1]),
-                          static_cast<const float*>(src[2]), static_cast<const int32_t*>(src[3]),
-                          static_cast<const float*>(src[4]), static_cast<const float*>(src[5]), M->tri_count,
-                          M->vertex_count};
+  RefitMeshDev d;
+  PRT_TRY(stage_mesh(c, M, dev_in, d));
   bool bad = false;
   PRT_TRY(refit_mesh(c, mi, d, true, dev_in ? nullptr : M->triangles, &bad));
   if (bad) return fail(PRT_ERR_INVALID_ARGUMENT, "mesh update: an index in device memory is out of range (vertex 0 was read in its place)");
@@ -365,6 +406,7 @@ int prt_set_mesh_skin(prt_ctx* c, int32_t mi, const prt_skin* S) {
   }
   SkinBinding& b = c->skin[mi];
   b.joints = 0;
+  b.skinned = false;
   if (!S) {
     b = SkinBinding();
     PRT_FOR_MEMBERS(prt_set_mesh_skin(m, mi, S));
@@ -429,7 +471,112 @@ int prt_skin_mesh(prt_ctx* c, int32_t mi, const float* M, int32_t J, uint32_t in
   RefitMeshDev r = {};
   r.triangles = reinterpret_cast<const float*>(d.triangles);
   PRT_TRY(refit_mesh(c, mi, r, false, nullptr, nullptr));
+  b.skinned = true;
   PRT_FOR_MEMBERS(prt_skin_mesh(m, mi, M, J, in_flags));
+  return PRT_OK;
+}
+
+int prt_rebuild_mesh(prt_ctx* c, int32_t mi, const prt_mesh* M, uint32_t in_flags, int32_t builder) {
+  if (!c) return fail(PRT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  if (in_flags & ~PRT_IN_DEVICE) return fail(PRT_ERR_INVALID_ARGUMENT, "unknown input flags");
+  PRT_TRY(mesh_arg(c, mi));
+  if (builder == PRT_BUILDER_HOST_SAH || builder == PRT_BUILDER_HOST_SBVH)
+    return fail(PRT_ERR_UNSUPPORTED, "mesh rebuild: the host builders rebuild through prt_set_meshes only");
+  if (builder != PRT_BUILDER_GPU_LBVH && builder != PRT_BUILDER_GPU_PLOC)
+    return fail(PRT_ERR_INVALID_ARGUMENT, "bad BLAS builder");
+  const bool dev_in = M && (in_flags & PRT_IN_DEVICE) != 0;
+  if (M) PRT_TRY(update_args(c, mi, M, in_flags, "mesh rebuild"));
+  else if (c->skin.size() != c->mesh_host.size() || !c->skin[mi].joints || !c->skin[mi].skinned)
+    return fail(PRT_ERR_NOT_READY, "mesh rebuild without arrays: no skin bound to the mesh, or no prt_skin_mesh on it yet");
+  PRT_JOIN(c);  // frames in flight complete first: they read the tree this call replaces
+  HIP_TRY(hipSetDevice(c->device));
+  MeshHost& mh = c->mesh_info[mi];
+  size_t most = 0;
+  for (const MeshHost& m : c->mesh_info) most = std::max(most, (size_t)m.tris);
+  HIP_TRY(c->rb_nodes.ensure(sizeof(Node8) * most));
+  HIP_TRY(c->rb_tris.ensure(sizeof(TriMT) * most));
+  RefitMeshDev d = {};
+  if (M) {
+    PRT_TRY(refit_scratch(c, !dev_in));
+    PRT_TRY(stage_mesh(c, M, dev_in, d));
+  } else {
+    d.triangles = reinterpret_cast<const float*>(c->skin[mi].dev.triangles);
+  }
+  // The build, into the context's scratch: the scene is untouched until it has succeeded.  The builder synchronises
+  // the context stream once per tree level; the wait before it is the bounded one of an RCCL context.
+  PRT_TRY(wait_stream(c, "prt_rebuild_mesh"));
+  GpuBlasInfo gi = {};
+  const hipError_t be = gpu_build_blas8(c->stream, d.triangles, mh.tris, max_leaf_tris(), c->rb_nodes.as<Node8>(),
+                                        c->rb_tris.as<TriMT>(), &gi, builder == PRT_BUILDER_GPU_PLOC);
+  if (be != hipSuccess) return fail(PRT_ERR_HIP, std::string("mesh rebuild: the device build failed: ") + hipGetErrorString(be));
+  constexpr int kMaxBlasDepth = 64;  // what the traversal stacks cover (depth_ok, prt_api.cpp)
+  if (gi.depth > kMaxBlasDepth) return fail(PRT_ERR_UNSUPPORTED, "mesh rebuild: the new BLAS is deeper than 64 levels");
+  if (gi.tris > mh.rec_cap) return fail(PRT_ERR_HIP, "mesh rebuild: more records than the mesh's region holds");
+  if ((int64_t)gi.nodes > mh.node_cap) PRT_TRY(grow_nodes(c, mi, gi.nodes));
+  // The commit, in the context stream's order: the nodes and records into the mesh's regions, the ShadeTri words of
+  // *M by the update's kernel (a skinned mesh's are there already), then the rebase and every primitive's record.
+  const MeshDev& md = c->mesh_host[mi];
+  Node8* nodes = c->nodes8.as<Node8>() + md.root;
+  TriMT* recs = c->tris.as<TriMT>() + mh.rec_base;
+  HIP_TRY(hipMemcpyAsync(nodes, c->rb_nodes.p, sizeof(Node8) * (size_t)gi.nodes, hipMemcpyDeviceToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(recs, c->rb_tris.p, sizeof(TriMT) * (size_t)gi.tris, hipMemcpyDeviceToDevice, c->stream));
+  RefitResult* res = c->rf.res.as<RefitResult>();
+  if (M) {
+    HIP_TRY(hipMemsetAsync(&res->bad_index, 0, 4, c->stream));
+    HIP_TRY(launch_refit_records(c->stream, nullptr, 0, c->stri.as<ShadeTri>() + md.prim_base, d, res));
+  }
+  HIP_TRY(gpu_blas_finish(c->stream, nodes, gi.nodes, md.root, recs, gi.tris, mh.rec_base, c->stri.as<ShadeTri>(),
+                          md.prim_base));
+  bool bad = false;
+  if (dev_in) {  // the bad-index flag of device arrays: the one host wait after the builder's
+    HIP_TRY(hipMemcpyAsync(c->rf.res_host, res, sizeof(RefitResult), hipMemcpyDeviceToHost, c->stream));
+    PRT_TRY(wait_stream(c, "reading the rebuilt mesh's index flag"));
+    bad = c->rf.res_host->bad_index != 0;
+  }
+  // everything derived from the tree
+  std::memcpy(mh.bmin, gi.bmin, sizeof(mh.bmin));
+  std::memcpy(mh.bmax, gi.bmax, sizeof(mh.bmax));
+  mh.depth = gi.depth;
+  mh.nodes = gi.nodes;
+  mh.leaves = gi.leaves;
+  mh.recs = gi.tris;
+  mh.level_ends.clear();  // the next update or skin reads the new nodes back once (refit_levels)
+  int maxd = 0;
+  for (const MeshHost& m : c->mesh_info) maxd = std::max(maxd, m.depth);
+  if (maxd != c->max_depth) {
+    // the stacks and spill columns are sized from max_depth at every launch; the instance BVH's depth cap was
+    // computed from it when the instance set was seeded (ensure_instances): the next update seeds again
+    c->max_depth = maxd;
+    c->tlas_n = -1;
+  }
+  c->inst_dirty = true;
+  c->tlas_dirty = true;
+  c->scene_epoch++;
+  if (bad) return fail(PRT_ERR_INVALID_ARGUMENT, "mesh rebuild: an index in device memory is out of range (vertex 0 was read in its place)");
+  PRT_FOR_MEMBERS(prt_rebuild_mesh(m, mi, M, in_flags, builder));
+  return PRT_OK;
+}
+
+int prt_blas_cost(prt_ctx* c, int32_t mi, double* cost) {
+  if (!c) return fail(PRT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  if (!cost) return fail(PRT_ERR_INVALID_ARGUMENT, "cost is NULL");
+  PRT_TRY(mesh_arg(c, mi));
+  PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
+  HIP_TRY(hipSetDevice(c->device));
+  const MeshHost& mh = c->mesh_info[mi];
+  // the partials of the largest tree the node array can hold, the root area and the result: one allocation
+  const size_t slots = (size_t)blas_cost_blocks(c->nodes_len) + 2;
+  if (c->cost_part.bytes < 8 * slots) {
+    PRT_TRY(wait_stream(c, "prt_blas_cost"));  // (an earlier call's kernels were waited for; a larger node array)
+    HIP_TRY(c->cost_part.ensure(8 * slots));
+  }
+  double* part = c->cost_part.as<double>();
+  double* out = part + (slots - 1);
+  HIP_TRY(launch_blas_cost(c->stream, c->nodes8.as<Node8>() + c->mesh_host[mi].root, (uint32_t)mh.nodes, part, out));
+  double v = 0.0;
+  HIP_TRY(hipMemcpyAsync(&v, out, 8, hipMemcpyDeviceToHost, c->stream));
+  PRT_TRY(wait_stream(c, "prt_blas_cost"));
+  *cost = v;
   return PRT_OK;
 }
 

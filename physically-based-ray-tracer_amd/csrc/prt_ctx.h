@@ -150,6 +150,7 @@ struct SkinBinding {
   DevBuf in, mats, work;
   SkinDev dev = {};
   int32_t joints = 0;
+  bool skinned = false;  // a prt_skin_mesh has run on this binding: `work` holds its fat triangles (prt_rebuild_mesh)
 };
 
 struct MeshHost {
@@ -164,6 +165,11 @@ struct MeshHost {
   uint32_t rec_base = 0, recs = 0;
   int32_t verts = 0;
   std::vector<uint32_t> level_ends;
+  // prt_rebuild_mesh: the sizes of the mesh's regions in the concatenated arrays, which a rebuilt tree must fit --
+  // node_cap nodes from MeshDev::root (what prt_set_meshes gave it, or the region a larger tree was moved to) and
+  // rec_cap records from rec_base (>= tris: the surplus of a spatial-split build goes unused after a rebuild)
+  int64_t node_cap = 0;
+  uint32_t rec_cap = 0;
 };
 
 // The scratch of the refit (prt_update_mesh / prt_skin_mesh, prt_blas_refit.h; prt_ctx::rf), allocated at a context's
@@ -197,6 +203,9 @@ struct prt_ctx {
   std::vector<prt::MeshDev> mesh_host;
   std::vector<prt::host::MeshHost> mesh_info;
   DevBuf nodes8, tris, stri, mesh;
+  // Node8 entries of nodes8 in use: the meshes' regions back to back (prt_rebuild_mesh appends a region for a tree
+  // that outgrew its mesh's; the region it leaves stays, unused).  The refit scratch is indexed by node position
+  uint64_t nodes_len = 0;
   int max_depth = 0;
   int builder = -1;  // BLAS builder (prt_set_bvh_builder): PRT_BUILDER_* (-1: PRT_BUILDER_HOST_SAH)
   double build_ms = 0;  // wall time of the last prt_set_meshes BLAS builds
@@ -227,6 +236,11 @@ struct prt_ctx {
   uint32_t* stage_flag = nullptr;      // one coherent pinned word per staging buffer (64-B stride): TlasJob::flag
   uint32_t* stage_flag_dev = nullptr;  // its device address
   prt::host::RefitScratch rf;  // prt_update_mesh / prt_skin_mesh
+  // prt_rebuild_mesh: where the device builder leaves a mesh's new tree before it is committed (room for T Node8 and
+  // T TriMT, T the largest mesh's triangle count; sized by the first rebuild after a prt_set_meshes and kept)
+  DevBuf rb_nodes, rb_tris;
+  // prt_blas_cost: the node pass's per-block sums and the root area, then the result (allocated at first use, kept)
+  DevBuf cost_part;
   DevBuf spill;  // traversal stack levels beyond the LDS ones (BVHs deeper than 17 levels)
   DevBuf diag;   // SceneDev::diag device counters ([0] traversal stack overflows, cumulative per context)
   // area light (prt_set_area_lights): p0, eu, ev, n, Le, area

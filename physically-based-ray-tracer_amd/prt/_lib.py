@@ -40,6 +40,7 @@ EXPORTS = [
     "prt_update_mesh", "prt_read_blas", "prt_read_blas_tris",
     "prt_snapshot_mesh", "prt_render_aov_deform", "prt_reproject_deform",
     "prt_set_mesh_skin", "prt_skin_mesh",
+    "prt_blas_cost", "prt_rebuild_mesh",
 ]
 SHARD_ID_BYTES = 128
 SHARD_NONE, SHARD_RCCL, SHARD_GROUP = 0, 1, 2  # prt_shard_info.transport
@@ -183,6 +184,8 @@ def load():
         "prt_snapshot_mesh": ([vp, i32], C.c_int),
         "prt_set_mesh_skin": ([vp, i32, C.POINTER(Skin)], C.c_int),
         "prt_skin_mesh": ([vp, i32, vp, i32, u32], C.c_int),
+        "prt_blas_cost": ([vp, i32, C.POINTER(C.c_double)], C.c_int),
+        "prt_rebuild_mesh": ([vp, i32, C.POINTER(Mesh), u32, i32], C.c_int),
         "prt_read_blas": ([vp, i32, vp, C.c_uint64, C.POINTER(C.c_uint64)], C.c_int),
         "prt_read_blas_tris": ([vp, i32, vp, C.c_uint64, C.POINTER(C.c_uint64)], C.c_int),
         "prt_set_instances": ([vp, vp, vp, i32], C.c_int),

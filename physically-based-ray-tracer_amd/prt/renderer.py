@@ -367,6 +367,13 @@ class Context:
         vertex_count attributes are required): the arrays are read in the context stream's order, the call waits for
         28 bytes, and an index out of range raises (the mesh is then traversable but unspecified until the next
         update)."""
+        m, keep = self._mesh_arg(mesh, device, "update_mesh")
+        check(self.L.prt_update_mesh(self.h, int(index), C.byref(m), _lib.IN_DEVICE if device else 0))
+        del keep
+
+    @staticmethod
+    def _mesh_arg(mesh, device, who):
+        """The prt_mesh of update_mesh / rebuild_mesh and the arrays it points into (kept alive by the caller)."""
         names = ("triangles", "fixed_normals", "fixed_uvs", "indices", "vertices", "face_normals")
         arrs = [getattr(mesh, n) for n in names]
         if not device:
@@ -379,7 +386,7 @@ class Context:
                 if hasattr(a, "data_ptr"):
                     want = "torch.int32" if n == "indices" else "torch.float32"
                     if not a.is_cuda or not a.is_contiguous() or str(a.dtype) != want:
-                        raise ValueError(f"update_mesh: {n} must be a contiguous {want} tensor on the device")
+                        raise ValueError(f"{who}: {n} must be a contiguous {want} tensor on the device")
                     ptrs.append(a.data_ptr())
                 else:
                     ptrs.append(int(a))
@@ -389,8 +396,27 @@ class Context:
                 tri_count = arrs[3].numel() // 3
             if verts is None:
                 verts = arrs[4].numel() // 3
-        m = _lib.Mesh(int(tri_count), int(verts), *ptrs, mesh.albedo, mesh.normal, mesh.metalness, mesh.emission)
-        check(self.L.prt_update_mesh(self.h, int(index), C.byref(m), _lib.IN_DEVICE if device else 0))
+        return _lib.Mesh(int(tri_count), int(verts), *ptrs, mesh.albedo, mesh.normal, mesh.metalness, mesh.emission), arrs
+
+    def rebuild_mesh(self, index, mesh=None, device=False, builder=_lib.BUILDER_GPU_PLOC):
+        """prt_rebuild_mesh: update_mesh with a fresh device build (builder: _lib.BUILDER_GPU_LBVH or BUILDER_GPU_PLOC)
+        in place of the refit.  `mesh` and `device` are update_mesh's; mesh=None rebuilds over the fat triangles the
+        mesh's skin binding holds from its last skin_mesh.  Blocks while the builder synchronises; a tree that outgrows
+        the mesh's node region drains the context once.  Decide when from blas_cost()."""
+        if mesh is None:
+            check(self.L.prt_rebuild_mesh(self.h, int(index), None, 0, int(builder)))
+            return
+        m, keep = self._mesh_arg(mesh, device, "rebuild_mesh")
+        check(self.L.prt_rebuild_mesh(self.h, int(index), C.byref(m), _lib.IN_DEVICE if device else 0, int(builder)))
+        del keep
+
+    def blas_cost(self, index):
+        """prt_blas_cost: the SAH cost of mesh `index`'s BLAS as it stands on the device (a float; the same tree gives
+        the same bits).  It grows as update_mesh / skin_mesh carry the mesh away from the pose its tree was built for
+        and falls back after rebuild_mesh."""
+        v = C.c_double()
+        check(self.L.prt_blas_cost(self.h, int(index), C.byref(v)))
+        return v.value
 
     def set_mesh_skin(self, index, skin):
         """prt_set_mesh_skin: binds `skin` (a scenes.Skin; None removes the binding) to mesh `index` of the last
@@ -983,6 +1009,18 @@ class Renderer:
         self.scene.update_model(index, mesh)
         self.ctx.update_mesh(index, mesh)
         self.ctx.reset_accumulation(full=True)
+
+    def RebuildModel(self, index, mesh=None, builder=_lib.BUILDER_GPU_PLOC):
+        """UpdateModel with a fresh device build of the model's BLAS in place of the refit (prt_rebuild_mesh); mesh=None
+        rebuilds over the pose of the last SkinModel.  BlasCost(index) tells when it pays: the library has no policy."""
+        if mesh is not None:
+            self.scene.update_model(index, mesh)
+        self.ctx.rebuild_mesh(index, mesh, builder=builder)
+        self.ctx.reset_accumulation(full=True)
+
+    def BlasCost(self, index):
+        """The SAH cost of model index's BLAS as it stands (prt_blas_cost)."""
+        return self.ctx.blas_cost(index)
 
     def SetSkin(self, index, skin):
         """scene.models[index] is skinned from now on (a scenes.Skin; None removes it): the scene keeps the skin and the
