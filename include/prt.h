@@ -317,6 +317,52 @@ int prt_set_lights(prt_ctx* ctx, const prt_lights* lights);
  * prt_set_instances with a different instance count.  Dielectric instances need bounces <= 4 with AA (5 without): the depth-first path tree
  * has up to 2^bounces - 1 segments per path. */
 int prt_set_instance_materials(prt_ctx* ctx, const int32_t* kinds, int32_t count);
+/* New transforms for the instances of the last prt_set_instances (additive in ABI 10; DESIGN.md 8 "Instance updates:
+ * the TLAS refit"; the definition: csrc/prt_tlas_refit.h): count row-major 4x4 matrices, laid out as prt_set_instances
+ * takes them.  The mesh indices and material kinds stay; count must equal the current instance count.
+ * The contract: afterwards every query, render and AOV returns, bit for bit, what a fresh context returns after
+ * prt_set_instances with these transforms and the same mesh indices (and the same prt_set_instance_materials): hits do
+ * not depend on the tree.  prt_stats.stack_overflows stays 0: the tree keeps its depth.
+ * The instance BVH (above 64 instances, or with PRT_TLAS=1; below that only the records change) is refitted, not
+ * rebuilt: the nodes, their slots, imask, meta, child_base, tri_base and the instance-slot table stay; leaf slot s of
+ * node j gets the box of instance slot[8j + s], an interior slot its child node's uninflated box, and every node is
+ * re-encoded bottom-up on the device, one launch per tree level.  A refit with the transforms the tree was built for
+ * reproduces the built bytes; updating to T' and back to T is byte-identical as well.  When to pay for a fresh SAH
+ * tree is the caller's decision: prt_tlas_cost measures the tree as it stands, prt_set_instances is the rebuild.
+ * in_flags = 0: host memory, copied before the call returns and uploaded in the context stream's order.  On a local
+ * group or RCCL context it applies to every member.
+ * in_flags = PRT_IN_DEVICE: device memory on the context's device, 16-byte aligned, read by one kernel in the context
+ * stream's order into storage of the library's own: nothing rereads the caller's memory after that kernel.  On a
+ * local group: PRT_ERR_UNSUPPORTED.  DEVICE-RESIDENT TRANSFORMS ARE A STATE that lasts until the next
+ * prt_set_instances or host-memory prt_update_instances: in it prt_set_instance_materials and the refresh that
+ * follows prt_update_mesh / prt_skin_mesh / prt_rebuild_mesh rebuild the records on the device from the transforms
+ * kept there, under the new kinds and mesh boxes, and refit the tree; the library holds no host copy of them.
+ * Ordering is prt_set_instances': the call does not join the frames in flight; it writes the next copy of the
+ * instance state once the context stream has waited for the frames that read that copy; frames enqueued before the
+ * call see the old instances, frames enqueued after it the new ones; kept primary hits and light visibility go
+ * stale.  The call never waits on the GPU, builds nothing on the host and gives the worker thread nothing.  The
+ * first call after a prt_set_instances waits (on the host only) until the worker has finished the builds queued
+ * before it, takes that tree's topology and uploads its level order; after that first call nothing is allocated.
+ * Transforms are not checked for finiteness: a non-finite one gives its instance the record prt_set_instances would,
+ * and the node boxes ignore a NaN coordinate, as the BLAS refit does.
+ * NULL context, NULL transforms, unknown flag bits, count different from the instance count, misaligned device
+ * memory: PRT_ERR_INVALID_ARGUMENT.  No meshes or no instances yet: PRT_ERR_NOT_READY.  A worker build that failed
+ * earlier is reported as prt_set_instances reports it.  Nothing changes in any of these cases. */
+int prt_update_instances(prt_ctx* ctx, const float* transforms, int32_t count, uint32_t in_flags);
+/* prt_blas_cost's measure (csrc/prt_blas_cost.h) of the instance BVH as it stands on the device; a leaf slot counts
+ * one instance.  0 when the rays walk the linear list.  The same two kernels, no atomics: two calls return the same
+ * bits.  The call joins the frames in flight and waits on the host once, for the 8 bytes of the result.  The library
+ * has no rebuild policy: compare the cost after a prt_set_instances (a fresh SAH tree) with the cost after N refits.
+ * NULL context or NULL cost: PRT_ERR_INVALID_ARGUMENT.  No meshes or no instances: PRT_ERR_NOT_READY. */
+int prt_tlas_cost(prt_ctx* ctx, double* cost);
+/* prt_read_blas's counterpart for the instance BVH, for tests and tools: the current tree's Node8 records (80 bytes
+ * each, node 0 the root; csrc/bvh_build.h) into nodes and the 8 instance-slot words per node (0xFFFFFFFF where a slot
+ * is no leaf slot) into slots, complete on return.  *nodes_needed / *slots_needed (each may be NULL) get the sizes in
+ * bytes; nodes == NULL or slots == NULL reports only the sizes; a buffer that is too small returns
+ * PRT_ERR_INVALID_ARGUMENT.  With the linear list both sizes are 0.  Joins the frames in flight and waits for the
+ * context stream. */
+int prt_read_tlas(prt_ctx* ctx, void* nodes, uint64_t node_bytes, uint32_t* slots, uint64_t slot_bytes,
+                  uint64_t* nodes_needed, uint64_t* slots_needed);
 /* count 0 (none) or 1 */
 int prt_set_area_lights(prt_ctx* ctx, const prt_area_light* lights, int32_t count);
 /* float RGB equirect, w*h*3; NULL/0 = no sky (misses shade 0 even with PRT_FLAG_SKYBOX) */

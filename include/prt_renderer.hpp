@@ -176,6 +176,13 @@ class Scene {
     check(prt_set_instances(ctx, xf.data(), mi.data(), (int32_t)mi.size()));
     check(prt_set_instance_materials(ctx, any ? mat.data() : nullptr, any ? (int32_t)mat.size() : 0));
   }
+  // the game objects moved (the same objects, models and materials): their transforms alone go to the device, where
+  // the instance BVH is refitted (prt_update_instances) -- no host build, no wait for the GPU
+  void UpdateInstances(prt_ctx* ctx) const {
+    std::vector<float> xf;
+    for (const GameObject& g : gameobjects) xf.insert(xf.end(), g.transform.begin(), g.transform.end());
+    check(prt_update_instances(ctx, xf.data(), (int32_t)gameobjects.size(), 0u));
+  }
 };
 
 // Camera (Core/Camera.h:11-31): position, target, the screen plane GetPrimaryRay interpolates, its basis
@@ -330,6 +337,26 @@ class Renderer {
   void ModelChanged(int32_t index) {
     scene.UpdateModel(ctx_, index);
     check(prt_reset_accumulation(ctx_, 1));
+  }
+
+  // scene.gameobjects moved (Scene::UpdateInstances): the instance BVH is refitted on the device and the accumulation
+  // restarts in full.  InstancesMovedDevice takes the transforms from device memory instead (16 floats per game
+  // object, 16-byte aligned, read in the context stream's order); scene.gameobjects then no longer says where the
+  // objects are.  TlasCost() is the SAH cost of the instance BVH as it stands (prt_tlas_cost): it grows while the refit
+  // follows the objects away from where the tree was built; scene.UploadInstances(ctx) builds a fresh tree.  When
+  // to rebuild is the caller's decision.
+  void InstancesMoved() {
+    scene.UpdateInstances(ctx_);
+    check(prt_reset_accumulation(ctx_, 1));
+  }
+  void InstancesMovedDevice(const float* transforms_dev) {
+    check(prt_update_instances(ctx_, transforms_dev, (int32_t)scene.gameobjects.size(), PRT_IN_DEVICE));
+    check(prt_reset_accumulation(ctx_, 1));
+  }
+  double TlasCost() const {
+    double v = 0.0;
+    check(prt_tlas_cost(ctx_, &v));
+    return v;
   }
 
   // The SAH cost of model index's BLAS as it stands (prt_blas_cost): it grows while ModelChanged / SkinModel refit

@@ -16,10 +16,13 @@
 #include <vector>
 
 #include "bvh_build.h"
+#include "prt_blas_cost_gpu.h"
 #include "prt_ctx.h"
 #include "prt_deform.h"
 #include "prt_denoise.h"
+#include "prt_mesh_host.h"
 #include "prt_motion.h"
+#include "prt_tlas_refit_gpu.h"
 
 using namespace prt;
 using namespace prt::host;
@@ -195,6 +198,173 @@ int prt::host::stage_release(prt_ctx*, StageSlot& st, hipStream_t s) {
 
 namespace {
 
+// the refit input of every instance (prt_refit.h) from the host's transforms, mesh boxes and kinds
+void fill_inst_src(const prt_ctx* c, InstSrc* src) {
+  const int32_t n = (int32_t)c->inst_mesh.size();
+  for (int32_t i = 0; i < n; i++) {
+    InstSrc& s = src[i];
+    const uint32_t m = c->inst_mesh[i];
+    std::memcpy(s.T, &c->inst_xf[16 * (size_t)i], sizeof(s.T));
+    const MeshHost& mh = c->mesh_info[m];
+    std::memcpy(s.bmin, mh.bmin, sizeof(s.bmin));
+    std::memcpy(s.bmax, mh.bmax, sizeof(s.bmax));
+    s.mesh = m;
+    s.kind = i < (int32_t)c->inst_kind.size() ? c->inst_kind[i] : 0u;
+  }
+}
+
+// prt_ctx::inst_tab: n mesh ids, n kinds, then two float4 per mesh, each part 16-byte aligned
+struct InstTabLayout { size_t kind, box, total; };
+InstTabLayout inst_tab_layout(size_t n, size_t nmesh) {
+  const size_t w = (4 * n + 15) & ~size_t(15);
+  return {w, 2 * w, 2 * w + 32 * nmesh};
+}
+
+// The device buffers of an instance state of n instances: every copy of the ring (frames in flight + 1) and the
+// scratch of prt_update_instances, sized for n (at least the linear-list size; a tree over n instances has at most
+// max(n, 1) nodes), so that later updates never reallocate.  A reallocation frees what queued frames read: it drains
+// first, a host wait.  Only a buffer that is too small is replaced (its contents are lost: a copy that holds the
+// current state is large enough).
+int size_instance_state(prt_ctx* c, int32_t n, bool use_tlas) {
+  if (c->isets.size() < (size_t)c->inflight + 1) c->isets.resize((size_t)c->inflight + 1);
+  const size_t cap = (size_t)std::max(n, kLinearInstances);
+  const size_t cap_nodes = (size_t)std::max(n, 1);
+  const size_t tab = inst_tab_layout(cap, c->mesh_host.size()).total;
+  bool fit = c->inst_tab.bytes >= tab &&
+             (!use_tlas || (c->tlas_order.bytes >= 4 * cap_nodes && c->tlas_box.bytes >= 24 * cap_nodes));
+  for (const InstSet& I : c->isets)
+    fit = fit && I.inst.bytes >= sizeof(InstDev) * cap && I.inst_src.bytes >= sizeof(InstSrc) * cap &&
+          (!use_tlas || (I.tlas8.bytes >= cap_nodes * sizeof(Node8) && I.tlas_slot.bytes >= cap_nodes * 32));
+  if (fit) return PRT_OK;
+  PRT_TRY(drain(c));
+  for (InstSet& I : c->isets) {
+    HIP_TRY(I.inst.ensure(sizeof(InstDev) * cap));
+    HIP_TRY(I.inst_src.ensure(sizeof(InstSrc) * cap));
+    if (use_tlas) {
+      HIP_TRY(I.tlas8.ensure(cap_nodes * sizeof(Node8)));
+      HIP_TRY(I.tlas_slot.ensure(cap_nodes * 32));
+    }
+  }
+  if (c->inst_tab.bytes < tab) {
+    HIP_TRY(c->inst_tab.ensure(tab));
+    c->inst_tab_ok = false;
+  }
+  if (use_tlas) {
+    if (c->tlas_order.bytes < 4 * cap_nodes) {
+      HIP_TRY(c->tlas_order.ensure(4 * cap_nodes));
+      c->tlas_topo = false;
+    }
+    HIP_TRY(c->tlas_box.ensure(24 * cap_nodes));
+  }
+  return PRT_OK;
+}
+
+// `bytes` of host memory into device memory at dst in the context stream's order: copied into a pinned staging
+// buffer now (the caller's memory is free on return), uploaded from there
+int stage_upload(prt_ctx* c, void* dst, const void* src, size_t bytes) {
+  StageSlot* st = nullptr;
+  PRT_TRY(stage_acquire(c, bytes, st));
+  st->lost = true;  // until the copy out of it is enqueued (a failure below leaves it out of the pool)
+  std::memcpy(st->p, src, bytes);
+  HIP_TRY(hipMemcpyAsync(dst, st->p, bytes, hipMemcpyHostToDevice, c->stream));
+  PRT_TRY(stage_release(c, *st, c->stream));
+  st->lost = false;
+  return PRT_OK;
+}
+
+int worker_ok(prt_ctx* c) {
+  if (!c->tlas_worker) return PRT_OK;
+  const TlasWorker::Stats ws = c->tlas_worker->stats();
+  if (ws.failed) return fail(PRT_ERR_HIP, "instance BVH build failed on the worker thread: " + ws.err);
+  return PRT_OK;
+}
+
+// The topology of the instance BVH the device holds (or will hold once the stream has run the queued uploads), once
+// per build: the worker's queue runs empty (a host condition variable, no GPU involved: at most the queued builds),
+// its last tree is what the last upload carries; tree_levels checks every link and orders the nodes by level, and
+// the order goes to tlas_order.  An update's staging buffer holds cap_nodes records of which only these are the
+// tree's: no kernel ever runs over more than tlas_nodes.
+int tlas_topology(prt_ctx* c, int32_t n) {
+  if (c->tlas_topo) return PRT_OK;
+  if (!c->tlas_worker) return fail(PRT_ERR_NOT_READY, "no instance BVH");
+  c->tlas_worker->wait_idle();
+  PRT_TRY(worker_ok(c));
+  std::vector<Node8> nodes;
+  std::vector<uint32_t> slot;
+  c->tlas_worker->last_tree(nodes, slot);
+  const size_t nn = nodes.size();
+  if (!nn || nn > (size_t)std::max(n, 1) || slot.size() != 8 * nn) return fail(PRT_ERR_HIP, "instance BVH: no usable tree");
+  std::vector<uint32_t> ends, order;
+  const char* err = nullptr;
+  if (!tree_levels(nodes.data(), nn, 0u, 0u, (uint32_t)(8 * nn), ends, order, &err))
+    return fail(PRT_ERR_HIP, std::string("instance BVH: ") + err);
+  PRT_TRY(stage_upload(c, c->tlas_order.p, order.data(), 4 * nn));
+  c->tlas_nodes = (uint32_t)nn;
+  c->tlas_level_ends = std::move(ends);
+  c->tlas_topo = true;
+  return PRT_OK;
+}
+
+// prt_update_instances and, while the transforms are device-resident, every refresh of the instance records: the
+// next copy of the instance state from new transforms (or from the same ones under new kinds or mesh boxes), with the
+// instance BVH refitted over it (prt_tlas_refit.h).  xf_dev: packed 4x4 matrices in device memory; null: the host's
+// inst_xf, or, while prt_ctx::xf_device, the transforms kept in the current copy's inst_src.  Everything is enqueued on
+// the context stream: no host build, no worker job, no wait for the GPU.
+int refit_instances(prt_ctx* c, const float* xf_dev) {
+  const int32_t n = (int32_t)c->inst_mesh.size();
+  const bool use_tlas = c->use_tlas;
+  const bool on_dev = xf_dev || c->xf_device;
+  PRT_TRY(worker_ok(c));
+  for (int32_t i = 0; i < n; i++)
+    if (c->inst_mesh[i] >= c->mesh_host.size()) return fail(PRT_ERR_INVALID_ARGUMENT, "instance references a missing mesh");
+  PRT_TRY(size_instance_state(c, n, use_tlas));
+  if (use_tlas) PRT_TRY(tlas_topology(c, n));
+  const size_t nx = (c->icur + 1) % c->isets.size();
+  InstSet& cur = c->isets[c->icur];
+  InstSet& X = c->isets[nx];
+  for (size_t k = 0; k < X.nuse; k++) HIP_TRY(hipStreamWaitEvent(c->stream, X.uses[k].second, 0));
+  X.nuse = 0;
+  if (!on_dev) {  // the records' input filled on the host, as ensure_instances fills it
+    c->inst_stage.resize(n);
+    fill_inst_src(c, c->inst_stage.data());
+    PRT_TRY(stage_upload(c, X.inst_src.p, c->inst_stage.data(), sizeof(InstSrc) * (size_t)n));
+    c->inst_tab_ok = false;  // (the table was not brought up to what this refill read)
+  } else {
+    const InstTabLayout L = inst_tab_layout((size_t)std::max(n, kLinearInstances), c->mesh_host.size());
+    if (!c->inst_tab_ok || c->inst_dirty) {  // mesh ids, kinds and the meshes' current root boxes
+      std::vector<char> tab(L.total, 0);
+      std::memcpy(tab.data(), c->inst_mesh.data(), 4 * (size_t)n);
+      if (!c->inst_kind.empty()) std::memcpy(tab.data() + L.kind, c->inst_kind.data(), 4 * std::min((size_t)n, c->inst_kind.size()));
+      for (size_t m = 0; m < c->mesh_info.size(); m++) {
+        std::memcpy(tab.data() + L.box + 32 * m, c->mesh_info[m].bmin, 12);
+        std::memcpy(tab.data() + L.box + 32 * m + 16, c->mesh_info[m].bmax, 12);
+      }
+      PRT_TRY(stage_upload(c, c->inst_tab.p, tab.data(), L.total));
+      c->inst_tab_ok = true;
+    }
+    const char* t = c->inst_tab.as<char>();
+    const InstTabDev tab = {reinterpret_cast<const uint32_t*>(t), reinterpret_cast<const uint32_t*>(t + L.kind),
+                            reinterpret_cast<const float4*>(t + L.box), (uint32_t)c->mesh_host.size()};
+    if (xf_dev) HIP_TRY(launch_inst_src(c->stream, reinterpret_cast<const float4*>(xf_dev), 4u, tab, n, X.inst_src.as<InstSrc>()));
+    else if (&X != &cur) HIP_TRY(launch_inst_src(c->stream, cur.inst_src.as<const float4>(), 6u, tab, n, X.inst_src.as<InstSrc>()));
+    else return fail(PRT_ERR_HIP, "instance update: one copy of the instance state");  // (the ring holds at least two)
+  }
+  HIP_TRY(launch_refit(c->stream, X.inst_src.as<InstSrc>(), n, X.inst.as<InstDev>()));
+  if (use_tlas)  // deepest level first, the root last: every child's box is written before its parent reads it
+    for (size_t lv = c->tlas_level_ends.size(); lv-- > 0;) {
+      const uint32_t b = lv ? c->tlas_level_ends[lv - 1] : 0u;
+      HIP_TRY(launch_tlas_refit_level(c->stream, cur.tlas8.as<Node8>(), cur.tlas_slot.as<uint32_t>(), X.tlas8.as<Node8>(),
+                                      X.tlas_slot.as<uint32_t>(), X.inst.as<InstDev>(), (uint32_t)n,
+                                      c->tlas_box.as<float>(), c->tlas_order.as<uint32_t>() + b,
+                                      c->tlas_level_ends[lv] - b, c->tlas_nodes));
+    }
+  c->icur = nx;
+  c->iset_n = n;
+  c->inst_dirty = false;
+  c->tlas_dirty = false;
+  return PRT_OK;
+}
+
 // Instance records on the device (prt_refit.h: MESA inverse, normal matrix, inflated world box): one async copy of
 // the transforms + k_refit on the render stream, so frames already queued keep reading the previous instances.
 // The instance BVH over those boxes (the same refit_instance on the host) is rebuilt for every update, as the
@@ -205,6 +375,9 @@ namespace {
 // copies the update's transforms; every frame walks the tree built over its own instances.
 int ensure_instances(prt_ctx* c) {
   if (!c->inst_dirty) return PRT_OK;
+  // device-resident transforms (prt_update_instances with PRT_IN_DEVICE): the host copy is stale; the records come
+  // from the transforms kept on the device, under the new kinds and mesh boxes, and the tree is refitted
+  if (c->xf_device) return refit_instances(c, nullptr);
   const int32_t n = (int32_t)c->inst_mesh.size();
   const char* te = std::getenv("PRT_TLAS");  // 1: the instance BVH at any instance count (tests)
   const bool use_tlas = n > kLinearInstances || (te && std::atoi(te) == 1);
@@ -212,32 +385,18 @@ int ensure_instances(prt_ctx* c) {
   // unchanged inverses and boxes, and the instance BVH is left as it is
   const bool tree_work = use_tlas && (c->tlas_dirty || !c->use_tlas || c->tlas_n != n);
   const bool async = tree_work && c->use_tlas && c->tlas_n == n && c->tlas_worker;
-  if (c->tlas_worker) {
-    const TlasWorker::Stats ws = c->tlas_worker->stats();
-    if (ws.failed) return fail(PRT_ERR_HIP, "instance BVH build failed on the worker thread: " + ws.err);
-  }
+  PRT_TRY(worker_ok(c));
   for (int32_t i = 0; i < n; i++)
     if (c->inst_mesh[i] >= c->mesh_host.size()) return fail(PRT_ERR_INVALID_ARGUMENT, "instance references a missing mesh");
-  auto fill = [&](InstSrc* src) {  // the refit input of every instance (prt_refit.h)
-    for (int32_t i = 0; i < n; i++) {
-      InstSrc& s = src[i];
-      const uint32_t m = c->inst_mesh[i];
-      std::memcpy(s.T, &c->inst_xf[16 * (size_t)i], sizeof(s.T));
-      const MeshHost& mh = c->mesh_info[m];
-      std::memcpy(s.bmin, mh.bmin, sizeof(s.bmin));
-      std::memcpy(s.bmax, mh.bmax, sizeof(s.bmax));
-      s.mesh = m;
-      s.kind = i < (int32_t)c->inst_kind.size() ? c->inst_kind[i] : 0u;
-    }
-  };
   // (filled in ordinary memory and copied into the pinned staging buffer in one memcpy: field-by-field stores into
   // pinned memory cost ~10 ms per 10,000 instances on the GPU box, profiles/r06_tlas_drift.txt)
   std::vector<InstSrc>& src = c->inst_stage;
   src.resize(n);
-  fill(src.data());
+  fill_inst_src(c, src.data());
   // the copy of the instance state this update writes: the next one in the ring (frames in flight + 1 copies), once
-  // the context stream has waited for the frames that read it
-  if (c->isets.size() < (size_t)c->inflight + 1) c->isets.resize((size_t)c->inflight + 1);
+  // the context stream has waited for the frames that read it.  Every copy and the scratch of prt_update_instances
+  // are sized here, for n, so that later updates never reallocate
+  PRT_TRY(size_instance_state(c, n, use_tlas));
   const size_t nx = (c->icur + 1) % c->isets.size();
   InstSet& cur = c->isets[c->icur];
   InstSet& X = c->isets[nx];
@@ -262,20 +421,7 @@ int ensure_instances(prt_ctx* c) {
            c->max_depth + depth_cap + 1 <= kMaxBvhDepth)
       depth_cap++;
   }
-  // buffers sized for n (at least the linear-list size; a tree over n instances has at most max(n, 1) nodes), so
-  // later updates never reallocate (a reallocation frees what queued frames read: it drains first, a host wait)
-  const size_t cap = (size_t)std::max(n, kLinearInstances);
-  const size_t cap_nodes = (size_t)std::max(n, 1);
-  if (X.inst.bytes < sizeof(InstDev) * cap || X.inst_src.bytes < sizeof(InstSrc) * cap ||
-      (use_tlas && (X.tlas8.bytes < cap_nodes * sizeof(Node8) || X.tlas_slot.bytes < cap_nodes * 32))) {
-    PRT_TRY(drain(c));
-    HIP_TRY(X.inst.ensure(sizeof(InstDev) * cap));
-    HIP_TRY(X.inst_src.ensure(sizeof(InstSrc) * cap));
-    if (use_tlas) {
-      HIP_TRY(X.tlas8.ensure(cap_nodes * sizeof(Node8)));
-      HIP_TRY(X.tlas_slot.ensure(cap_nodes * 32));
-    }
-  }
+  const size_t cap_nodes = (size_t)std::max(n, 1);  // a tree over n instances has at most max(n, 1) nodes
   // uploads through one pinned staging slot: the instance sources, then the tree's nodes and slots
   const size_t sb_src = sizeof(InstSrc) * (size_t)n;
   const size_t sb_nodes = !tree_work ? 0 : async ? cap_nodes * sizeof(Node8) : tree.nodes.size() * sizeof(Node8);
@@ -349,6 +495,9 @@ int ensure_instances(prt_ctx* c) {
     c->tlas_async++;
   }
   c->icur = nx;
+  c->iset_n = n;
+  c->inst_tab_ok = false;            // (a device-side refill uploads what this one read)
+  if (tree_work) c->tlas_topo = false;  // a new tree: the next prt_update_instances takes its topology
   c->inst_dirty = false;
   c->tlas_dirty = false;
   return PRT_OK;
@@ -629,6 +778,7 @@ int prt_set_instances(prt_ctx* c, const float* xf, const uint32_t* mi, int32_t n
   c->inst_xf.assign(xf, xf + 16 * (size_t)n);
   if ((size_t)n != c->inst_mesh.size()) c->inst_kind.clear();  // materials survive transform updates only
   c->inst_mesh.assign(mi, mi + n);
+  c->xf_device = false;  // the host copy is current again (prt_update_instances with device transforms made it stale)
   c->inst_dirty = true;
   c->tlas_dirty = true;
   c->inst_epoch++;  // transforms, boxes, the instance BVH and the hit word's instance bits: kept primary hits are stale
@@ -661,6 +811,101 @@ int prt_set_instance_materials(prt_ctx* c, const int32_t* kinds, int32_t n) {
   }
   PRT_FOR_MEMBERS(prt_set_instance_materials(m, kinds, n));
   return PRT_OK;
+}
+
+int prt_update_instances(prt_ctx* c, const float* xf, int32_t n, uint32_t in_flags) {
+  if (!c || !xf) return fail(PRT_ERR_INVALID_ARGUMENT, "bad instance update arguments");
+  if (in_flags & ~PRT_IN_DEVICE) return fail(PRT_ERR_INVALID_ARGUMENT, "unknown input flags");
+  if (c->mesh_host.empty()) return fail(PRT_ERR_NOT_READY, "no meshes: call prt_set_meshes");
+  if (c->inst_mesh.empty()) return fail(PRT_ERR_NOT_READY, "no instances: call prt_set_instances");
+  if (n != (int32_t)c->inst_mesh.size())
+    return fail(PRT_ERR_INVALID_ARGUMENT, "instance update: the instance count must stay (a new set needs prt_set_instances)");
+  const bool dev_in = (in_flags & PRT_IN_DEVICE) != 0;
+  if (dev_in && c->sh_kind == 2) return fail(PRT_ERR_UNSUPPORTED, "device transforms on a local shard group");
+  if (dev_in && (reinterpret_cast<uintptr_t>(xf) & 15u))
+    return fail(PRT_ERR_INVALID_ARGUMENT, "device transforms must be 16-byte aligned");
+  PRT_TRY(worker_ok(c));
+  // (no join of the frames in flight: the update writes the next copy of the instance state, InstSet)
+  HIP_TRY(hipSetDevice(c->device));
+  if (!dev_in) {
+    c->inst_xf.assign(xf, xf + 16 * (size_t)n);
+    c->xf_device = false;
+  }
+  const bool first = c->iset_n != n;
+  if (first) {  // the set was never brought to the device (prt_set_instances came before the meshes): its first
+    c->inst_dirty = true;  // build, from the host's transforms; device transforms then move it
+    c->tlas_dirty = true;
+    PRT_TRY(ensure_instances(c));
+  }
+  if (dev_in || !first) PRT_TRY(refit_instances(c, dev_in ? xf : nullptr));
+  if (dev_in) c->xf_device = true;
+  c->inst_epoch++;  // transforms, boxes and the instance BVH changed: kept primary hits and light visibility are stale
+  PRT_FOR_MEMBERS(prt_update_instances(m, xf, n, in_flags));
+  return PRT_OK;
+}
+
+namespace {
+// the instance state as the next frame reads it, and the live tree's node count (0: the rays walk the linear list)
+int tlas_current(prt_ctx* c, uint32_t& n_nodes) {
+  if (c->mesh_host.empty()) return fail(PRT_ERR_NOT_READY, "no meshes: call prt_set_meshes");
+  if (c->inst_mesh.empty()) return fail(PRT_ERR_NOT_READY, "no instances: call prt_set_instances");
+  PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
+  HIP_TRY(hipSetDevice(c->device));
+  PRT_TRY(ensure_instances(c));
+  n_nodes = 0;
+  if (!c->use_tlas) return PRT_OK;
+  if (c->tlas_topo) {
+    n_nodes = c->tlas_nodes;
+  } else {  // the worker's last tree is the one the stream uploads last (tlas_topology)
+    if (!c->tlas_worker) return fail(PRT_ERR_NOT_READY, "no instance BVH");
+    c->tlas_worker->wait_idle();
+    PRT_TRY(worker_ok(c));
+    n_nodes = (uint32_t)c->tlas_worker->last_tree_nodes();
+  }
+  return PRT_OK;
+}
+}  // namespace
+
+int prt_tlas_cost(prt_ctx* c, double* cost) {
+  if (!c) return fail(PRT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  if (!cost) return fail(PRT_ERR_INVALID_ARGUMENT, "cost is NULL");
+  uint32_t nn = 0;
+  PRT_TRY(tlas_current(c, nn));
+  if (!nn) {
+    *cost = 0.0;
+    return PRT_OK;
+  }
+  const size_t slots = (size_t)blas_cost_blocks(nn) + 2;  // the blocks' sums, the root area, the result
+  if (c->cost_part.bytes < 8 * slots) {
+    PRT_TRY(wait_stream(c, "prt_tlas_cost"));  // (an earlier call's kernels were waited for; a larger tree)
+    HIP_TRY(c->cost_part.ensure(8 * slots));
+  }
+  double* part = c->cost_part.as<double>();
+  double* out = part + (slots - 1);
+  HIP_TRY(launch_blas_cost(c->stream, c->isets[c->icur].tlas8.as<Node8>(), nn, part, out));
+  double v = 0.0;
+  HIP_TRY(hipMemcpyAsync(&v, out, 8, hipMemcpyDeviceToHost, c->stream));
+  PRT_TRY(wait_stream(c, "prt_tlas_cost"));
+  *cost = v;
+  return PRT_OK;
+}
+
+int prt_read_tlas(prt_ctx* c, void* nodes, uint64_t node_bytes, uint32_t* slots, uint64_t slot_bytes,
+                  uint64_t* nodes_needed, uint64_t* slots_needed) {
+  if (!c) return fail(PRT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  uint32_t nn = 0;
+  PRT_TRY(tlas_current(c, nn));
+  const uint64_t nb = (uint64_t)nn * sizeof(Node8), sb = (uint64_t)nn * 32;
+  if (nodes_needed) *nodes_needed = nb;
+  if (slots_needed) *slots_needed = sb;
+  if (!nodes || !slots) return PRT_OK;
+  if (node_bytes < nb || slot_bytes < sb) return fail(PRT_ERR_INVALID_ARGUMENT, "prt_read_tlas: buffer too small");
+  if (nn) {
+    const InstSet& I = c->isets[c->icur];
+    HIP_TRY(hipMemcpyAsync(nodes, I.tlas8.p, nb, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(slots, I.tlas_slot.p, sb, hipMemcpyDeviceToHost, c->stream));
+  }
+  return wait_stream(c, "prt_read_tlas");
 }
 
 int prt_set_area_lights(prt_ctx* c, const prt_area_light* a, int32_t n) {

@@ -248,6 +248,23 @@ struct prt_ctx {
   int32_t area = 0, area_two_sided = 0;
   bool inst_dirty = true;  // the device instance records (k_refit) are out of date
   bool tlas_dirty = true;  // transforms or meshes changed since the instance BVH was last built / refitted
+  // prt_update_instances (prt_tlas_refit.h): new transforms for the instance set, the instance BVH refitted on the
+  // device.  iset_n: the instance count isets[icur] was last written for (-1: never).  xf_device: the transforms
+  // came from device memory and live in isets[icur].inst_src alone -- inst_xf is stale and nothing reads it; every
+  // refresh of the records (ensure_instances) goes through the device path until the next prt_set_instances or
+  // host-memory update.  The live tree's topology, taken from the worker's last tree at the first update after a
+  // build and kept until the next build: tlas_nodes nodes, ordered by level in tlas_order (level d's nodes are
+  // tlas_order[tlas_level_ends[d - 1] .. tlas_level_ends[d])); tlas_box: six floats per node of scratch.  inst_tab:
+  // what a device-side refill needs besides the transforms -- mesh ids, kinds, then the per-mesh boxes -- uploaded
+  // when it is not what the host holds (inst_tab_ok; the records were dirty, or a host-side refill came between).
+  // All sized with the instance sets (ensure_instances)
+  int32_t iset_n = -1;
+  bool xf_device = false;
+  bool tlas_topo = false;
+  uint32_t tlas_nodes = 0;
+  std::vector<uint32_t> tlas_level_ends;
+  DevBuf tlas_order, tlas_box, inst_tab;
+  bool inst_tab_ok = false;
   // sky, lights, camera
   DevBuf sky;
   int32_t skyw = 0, skyh = 0;

@@ -55,6 +55,22 @@ class TlasWorker {
     }
     cv_.notify_all();
   }
+  // prt_update_instances refits the tree the device holds: wait until every submitted job has finished (a host
+  // condition variable: no GPU involved, bounded by the queued builds), then copy that tree out -- the last good one,
+  // which is what the last job left in its update's staging buffer
+  void wait_idle() {
+    std::unique_lock<std::mutex> g(m_);
+    idle_cv_.wait(g, [&] { return q_.empty() && !busy_; });
+  }
+  void last_tree(std::vector<Node8>& nodes, std::vector<uint32_t>& slot) {
+    std::lock_guard<std::mutex> g(m_);
+    nodes = good_nodes_;
+    slot = good_slot_;
+  }
+  size_t last_tree_nodes() {
+    std::lock_guard<std::mutex> g(m_);
+    return good_nodes_.size();
+  }
   // diagnostics of the finished jobs
   struct Stats { double ms = 0, cpu_ms = 0; int32_t median = 0, failed = 0; std::string err; };
   Stats stats() {
@@ -72,6 +88,7 @@ class TlasWorker {
         if (q_.empty()) return;  // stop_ with nothing queued
         j = q_.front();
         q_.pop_front();
+        busy_ = true;
       }
       const auto t0 = std::chrono::steady_clock::now();
       timespec c0{}, c1{};
@@ -112,12 +129,14 @@ class TlasWorker {
       st_.cpu_ms = (c1.tv_sec - c0.tv_sec) * 1e3 + (c1.tv_nsec - c0.tv_nsec) * 1e-6;
       st_.median += median ? 1 : 0;
       __atomic_store_n(j->flag, 1u, __ATOMIC_RELEASE);  // the tree is in dst: the stream's wait ends
+      busy_ = false;
+      idle_cv_.notify_all();
     }
   }
   std::mutex m_;
-  std::condition_variable cv_;
+  std::condition_variable cv_, idle_cv_;
   std::deque<std::shared_ptr<TlasJob>> q_;
-  bool stop_ = false;
+  bool stop_ = false, busy_ = false;  // busy_: a job was taken off the queue and has not finished
   std::vector<Node8> good_nodes_;
   std::vector<uint32_t> good_slot_;
   Stats st_;

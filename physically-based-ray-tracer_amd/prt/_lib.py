@@ -14,7 +14,7 @@ ABI_VERSION = 10  # PRT_ABI_VERSION of the include/prt.h these structs mirror
 FLAG_AA, FLAG_ACCUMULATE, FLAG_GAMMA, FLAG_NORMALMAP, FLAG_SKYBOX, FLAG_LIGHTED, FLAG_STOCHASTIC = (1 << i for i in range(7))
 FLAGS_DEFAULT = 0x7F
 OUT_DEVICE = 1
-IN_DEVICE = 1  # prt_update_mesh / prt_skin_mesh: the mesh's arrays / the joint matrices are device memory
+IN_DEVICE = 1  # prt_update_mesh / prt_skin_mesh / prt_update_instances: the arrays / matrices / transforms are device memory
 OUT_TIMED = 2  # prt_render_aov / prt_denoise: record the per-pass HIP events prt_denoise_timings reads
 DENOISE_TIMINGS = 10
 BUILDER_HOST_SAH, BUILDER_GPU_LBVH, BUILDER_HOST_SBVH, BUILDER_GPU_PLOC = 0, 1, 2, 3
@@ -41,6 +41,7 @@ EXPORTS = [
     "prt_snapshot_mesh", "prt_render_aov_deform", "prt_reproject_deform",
     "prt_set_mesh_skin", "prt_skin_mesh",
     "prt_blas_cost", "prt_rebuild_mesh",
+    "prt_update_instances", "prt_tlas_cost", "prt_read_tlas",
 ]
 SHARD_ID_BYTES = 128
 SHARD_NONE, SHARD_RCCL, SHARD_GROUP = 0, 1, 2  # prt_shard_info.transport
@@ -189,6 +190,9 @@ def load():
         "prt_read_blas": ([vp, i32, vp, C.c_uint64, C.POINTER(C.c_uint64)], C.c_int),
         "prt_read_blas_tris": ([vp, i32, vp, C.c_uint64, C.POINTER(C.c_uint64)], C.c_int),
         "prt_set_instances": ([vp, vp, vp, i32], C.c_int),
+        "prt_update_instances": ([vp, vp, i32, u32], C.c_int),
+        "prt_tlas_cost": ([vp, C.POINTER(C.c_double)], C.c_int),
+        "prt_read_tlas": ([vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int),
         "prt_set_lights": ([vp, C.POINTER(Lights)], C.c_int),
         "prt_set_sky": ([vp, vp, i32, i32], C.c_int),
         "prt_set_camera": ([vp, C.POINTER(CameraDesc)], C.c_int),

@@ -359,6 +359,49 @@ class Context:
         mi = np.ascontiguousarray([m for m, _ in blases], np.uint32)
         check(self.L.prt_set_instances(self.h, xf.ctypes.data, mi.ctypes.data, len(blases)))
 
+    def update_instances(self, transforms, device=False):
+        """prt_update_instances: the instances of the last set_instances / set_scene take new transforms; mesh indices
+        and material kinds stay, and the instance BVH is refitted on the device (no host build, no wait for the GPU).
+        `transforms`: a float32 array of shape (n, 4, 4) or (16 n,), row-major; with device=True a contiguous float32
+        torch tensor of 16 n elements on this context's device, or a raw device pointer as (pointer, n), read by one
+        kernel in the context stream's order.  Device transforms stay on the device: until the next set_instances or
+        host update the context holds no host copy of them.  tlas_cost() tells when set_instances (a fresh SAH tree)
+        is worth its build."""
+        if device:
+            if hasattr(transforms, "data_ptr"):
+                if not transforms.is_cuda or not transforms.is_contiguous() or str(transforms.dtype) != "torch.float32" \
+                        or transforms.numel() % 16:
+                    raise ValueError("update_instances: transforms must be a contiguous torch.float32 tensor of 16 per "
+                                     "instance on the device")
+                ptr, n = transforms.data_ptr(), transforms.numel() // 16
+            else:
+                ptr, n = transforms
+            check(self.L.prt_update_instances(self.h, int(ptr), int(n), _lib.IN_DEVICE))
+            return
+        xf = _f32(transforms).reshape(-1)
+        if xf.size % 16:
+            raise ValueError("update_instances: 16 floats per instance")
+        check(self.L.prt_update_instances(self.h, xf.ctypes.data, xf.size // 16, 0))
+
+    def tlas_cost(self):
+        """prt_tlas_cost: the SAH cost of the instance BVH as it stands on the device (prt_blas_cost's measure, a leaf
+        slot counting one instance; 0.0 on the linear list).  It grows as update_instances carries the instances away
+        from where the tree was built and falls back after set_instances."""
+        v = C.c_double()
+        check(self.L.prt_tlas_cost(self.h, C.byref(v)))
+        return v.value
+
+    def read_tlas(self):
+        """prt_read_tlas: the instance BVH's Node8 records as a uint8 array [nodes, 80] and its instance-slot table as a
+        uint32 array [nodes, 8] (0xFFFFFFFF where a slot is no leaf slot); both empty on the linear list.  Introspection
+        for tests and tools; waits for the context stream."""
+        nb, sb = C.c_uint64(), C.c_uint64()
+        check(self.L.prt_read_tlas(self.h, None, 0, None, 0, C.byref(nb), C.byref(sb)))
+        nodes, slots = np.zeros(nb.value, np.uint8), np.zeros(sb.value // 4, np.uint32)
+        if nb.value:
+            check(self.L.prt_read_tlas(self.h, nodes.ctypes.data, nb.value, slots.ctypes.data, sb.value, None, None))
+        return nodes.reshape(-1, 80), slots.reshape(-1, 8)
+
     def update_mesh(self, index, mesh, device=False):
         """prt_update_mesh: mesh `index` of the last set_scene takes `mesh`'s arrays and its BLAS is refitted in place
         (same triangle and vertex counts, same texture ids; the tree keeps its topology).  `mesh` is a scenes.Mesh of
@@ -1009,6 +1052,25 @@ class Renderer:
         self.scene.update_model(index, mesh)
         self.ctx.update_mesh(index, mesh)
         self.ctx.reset_accumulation(full=True)
+
+    def UpdateInstances(self, transforms, device=False):
+        """scene.blases moved to `transforms` (one 4x4 per instance, the models stay): the context takes them and refits
+        its instance BVH on the device (prt_update_instances), where Tick-time set_instances would rebuild it on the
+        host.  Host transforms ((n, 4, 4) float32) also replace those in scene.blases; with device=True (a torch
+        tensor on the context's device) the scene's host copy is left as it is and is stale until the next host
+        update -- TickTemporal(motion=True), which hands scene.blases to the context, wants a host copy.  The
+        accumulation is reset in full, as by UpdateModel.  TlasCost() tells when a set_instances pays."""
+        if not device:
+            T = _f32(transforms).reshape(-1, 4, 4)
+            if len(T) != len(self.scene.blases):
+                raise ValueError("UpdateInstances: one transform per instance")
+            self.scene.blases = [(m, T[i].copy()) for i, (m, _) in enumerate(self.scene.blases)]
+        self.ctx.update_instances(transforms, device=device)
+        self.ctx.reset_accumulation(full=True)
+
+    def TlasCost(self):
+        """The SAH cost of the instance BVH as it stands (prt_tlas_cost)."""
+        return self.ctx.tlas_cost()
 
     def RebuildModel(self, index, mesh=None, builder=_lib.BUILDER_GPU_PLOC):
         """UpdateModel with a fresh device build of the model's BLAS in place of the refit (prt_rebuild_mesh); mesh=None
