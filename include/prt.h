@@ -427,6 +427,17 @@ int prt_primary_rays(prt_ctx* ctx, uint64_t* traced, uint64_t* reused, int32_t r
  * summed over its members); reset != 0 zeroes it after reading.  A skipped shadow ray is still a shadow ray of its
  * path: prt_ray_totals and prt_stats count it. */
 int prt_shadow_reuse(prt_ctx* ctx, uint64_t* reused, int32_t reset);
+/* Primary-surface reuse counter (additive within ABI 10).  What the shading of a pixel's fixed path-1 primary hit
+ * reads before any random draw -- the shading normal, the material, the hit point, or the sky radiance of a miss --
+ * repeats while the primary hits (above), the textures, the sky, the instance materials and the call's
+ * PRT_FLAG_NORMALMAP and PRT_FLAG_SKYBOX bits stay put.  In the plain wavefront pipeline (render mode 0, no area
+ * light or dielectrics, not the merged small-call form) the first call that reuses the primary hits keeps those values
+ * per pixel and later calls shade from them (bit-identical images; PRT_SURFACE_REUSE=0 in the environment switches
+ * only this off, PRT_SHADOW_REUSE=0 and PRT_PRIMARY_REUSE=0 switch it off too; PRT_INIT_FOLD=0 keeps the wave-init
+ * launch in front of a pass that shades from the kept values).  Lights are no part of it.  reused:
+ * the work items (pixels x reference frames) shaded from the kept values by the calls so far; host bookkeeping like
+ * prt_primary_rays, no wait (a local group: summed over its members); reset != 0 zeroes it after reading. */
+int prt_surface_reuse(prt_ctx* ctx, uint64_t* reused, int32_t reset);
 /* Dead shadow-ray counter (additive within ABI 10).  A next-event shadow ray is dead when the factor its visibility
  * answer is multiplied by is exactly zero: PRT_FLAG_LIGHTED is off, or every channel of its unoccluded contribution
  * compares equal to zero (the light is behind the shading normal, the hit point is outside the spot's cone, the

@@ -420,6 +420,12 @@ class Renderer {
     check(prt_shadow_reuse(ctx_, &reused, reset ? 1 : 0));
     return reused;
   }
+  // work items whose primary hit was shaded from the kept surface values so far (prt_surface_reuse; host counter)
+  uint64_t SurfaceReuse(bool reset = false) const {
+    uint64_t reused = 0;
+    check(prt_surface_reuse(ctx_, &reused, reset ? 1 : 0));
+    return reused;
+  }
   // shadow rays counted instead of traced because their contribution is zero so far (prt_shadow_dead; waits)
   uint64_t ShadowDead(bool reset = false) const {
     uint64_t dead = 0;

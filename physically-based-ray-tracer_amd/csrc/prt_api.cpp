@@ -753,6 +753,7 @@ int prt_finish(prt_ctx* c) {
 int prt_set_textures(prt_ctx* c, const prt_texture* t, int32_t n) {
   if (!c || (n > 0 && !t) || n < 0) return fail(PRT_ERR_INVALID_ARGUMENT, "bad textures");
   PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
+  c->shade_epoch++;  // what a kept primary surface was shaded from changes (prt_ctx::shade_epoch)
   std::vector<uint32_t> all;
   std::vector<TexDev> host(n);
   for (int32_t i = 0; i < n; i++) {
@@ -781,6 +782,7 @@ int prt_set_instances(prt_ctx* c, const float* xf, const uint32_t* mi, int32_t n
   c->xf_device = false;  // the host copy is current again (prt_update_instances with device transforms made it stale)
   c->inst_dirty = true;
   c->tlas_dirty = true;
+  c->shade_epoch++;
   c->inst_epoch++;  // transforms, boxes, the instance BVH and the hit word's instance bits: kept primary hits are stale
   HIP_TRY(hipSetDevice(c->device));
   if (!c->mesh_host.empty()) {
@@ -804,6 +806,7 @@ int prt_set_instance_materials(prt_ctx* c, const int32_t* kinds, int32_t n) {
   // No inst_epoch bump: a kept primary hit is (t, u, v, prim | inst << pbits), and a materials-only update moves no
   // transform, box or tree (ensure_instances) and leaves pbits alone; the kind is read at shading, from the
   // instance record.  Dielectric kinds switch to the extension kernels, which neither read nor write phit.
+  c->shade_epoch++;  // ... but a kept primary surface holds the material the kind shaped
   c->inst_dirty = true;
   HIP_TRY(hipSetDevice(c->device));
   if (!c->mesh_host.empty() && !c->inst_mesh.empty()) {
@@ -839,6 +842,7 @@ int prt_update_instances(prt_ctx* c, const float* xf, int32_t n, uint32_t in_fla
   }
   if (dev_in || !first) PRT_TRY(refit_instances(c, dev_in ? xf : nullptr));
   if (dev_in) c->xf_device = true;
+  c->shade_epoch++;
   c->inst_epoch++;  // transforms, boxes and the instance BVH changed: kept primary hits and light visibility are stale
   PRT_FOR_MEMBERS(prt_update_instances(m, xf, n, in_flags));
   return PRT_OK;
@@ -943,6 +947,7 @@ int prt_set_lights(prt_ctx* c, const prt_lights* l) {
 int prt_set_sky(prt_ctx* c, const float* rgb, int32_t w, int32_t h) {
   if (!c) return fail(PRT_ERR_INVALID_ARGUMENT, "ctx is NULL");
   PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
+  c->shade_epoch++;  // what a kept primary surface was shaded from changes (prt_ctx::shade_epoch)
   PRT_TRY(drain(c));
   if (!rgb || w <= 0 || h <= 0) {
     c->skyw = c->skyh = 0;

@@ -123,6 +123,7 @@ int refit_mesh(prt_ctx* c, int32_t mi, const RefitMeshDev& d, bool shade, const 
   }
   c->inst_dirty = true;
   c->tlas_dirty = true;
+  c->shade_epoch++;
   c->scene_epoch++;
   return PRT_OK;
 }
@@ -329,6 +330,7 @@ int prt_set_meshes(prt_ctx* c, const prt_mesh* m_in, int32_t n) {
   c->skin.clear();  // the skin bindings of the previous meshes (prt_set_mesh_skin), likewise
   c->inst_dirty = true;
   c->tlas_dirty = true;
+  c->shade_epoch++;
   c->scene_epoch++;  // new geometry and BLASes (and prim bits of the hit word): kept primary hits are stale
   PRT_FOR_MEMBERS(prt_set_meshes(m, m_in, n));
   return PRT_OK;
@@ -551,6 +553,7 @@ int prt_rebuild_mesh(prt_ctx* c, int32_t mi, const prt_mesh* M, uint32_t in_flag
   }
   c->inst_dirty = true;
   c->tlas_dirty = true;
+  c->shade_epoch++;
   c->scene_epoch++;
   if (bad) return fail(PRT_ERR_INVALID_ARGUMENT, "mesh rebuild: an index in device memory is out of range (vertex 0 was read in its place)");
   PRT_FOR_MEMBERS(prt_rebuild_mesh(m, mi, M, in_flags, builder));
@@ -610,6 +613,7 @@ int prt_set_bvh_builder(prt_ctx* c, int32_t builder) {
   if (!c || builder < PRT_BUILDER_HOST_SAH || builder > PRT_BUILDER_GPU_PLOC)
     return fail(PRT_ERR_INVALID_ARGUMENT, "bad BLAS builder");
   c->builder = builder;
+  c->shade_epoch++;
   c->scene_epoch++;  // (the BLASes change at the next prt_set_meshes, which bumps it again)
   PRT_FOR_MEMBERS(prt_set_bvh_builder(m, builder));
   return PRT_OK;

@@ -130,6 +130,13 @@ PrimKey prim_key(const prt_ctx* c, const SceneDev& S, const TileMap& M) {
   return k;
 }
 
+// some mesh has an emission texture: the primary-surface record needs its emission plane
+bool surf_emissive(const prt_ctx* c) {
+  for (const MeshDev& m : c->mesh_host)
+    if (m.tex[3] >= 0) return true;
+  return false;
+}
+
 int prepare_render(prt_ctx* c, const prt_render_params* p, const TileMap& M, int32_t rank, RenderPlan& R,
                    Flight* fl = nullptr) {
   SceneDev& S = R.S;
@@ -173,6 +180,13 @@ int prepare_render(prt_ctx* c, const prt_render_params* p, const TileMap& M, int
     const void* lbefore = ws.lvis.p;
     HIP_TRY(ws.lvis.ensure(sizeof(uint2) * (size_t)P.per));
     if (ws.lvis.p != lbefore) ws.lvalid = false;
+  }
+  if (P.sreuse) {  // and of the primary-surface record: three 16-byte words per entry, the emission plane if needed
+    const void* sbefore = ws.surf.p;
+    const void* ebefore = ws.surf_e.p;
+    HIP_TRY(ws.surf.ensure(3 * round256(sizeof(float4) * (size_t)P.per)));
+    if (surf_emissive(c)) HIP_TRY(ws.surf_e.ensure(sizeof(float4) * (size_t)P.per));
+    if (ws.surf.p != sbefore || ws.surf_e.p != ebefore) ws.svalid = false;
   }
   return PRT_OK;
 }
@@ -294,11 +308,36 @@ int enqueue_render_body(prt_ctx* c, const prt_render_params* p, const TileMap& M
     // per-item records; k_wave_init clears the status words of plane 0
     WaveBufs wb = ws0.wb;
     if (P.defer()) point_planes(wb, ws0.planes, (uint32_t)nb, iters);
-    HIP_TRY(launch_wave_init(Lw, S, A, M, wb, frames));
     const bool lrec = wb.pmode == kPrimReuse && wb.lvis != nullptr;  // the pass uses and fills the record
+    // the primary-surface record: valid for the primary hits it was filled on, the shading epoch, the two flags its
+    // values depend on and the presence of the emission plane.  A stale one is refilled by this pass's iteration 0
+    // (every entry is rewritten: no clearing) and stamped once the pass is enqueued, in stream order as phit's stamp
+    const uint32_t sfl = p->flags & (PRT_FLAG_NORMALMAP | PRT_FLAG_SKYBOX);
+    const bool semis = surf_emissive(c);
+    const int surf = surface_form(P, lrec, ws0.svalid && ws0.sgen == ws0.pgen && ws0.sepoch == c->shade_epoch &&
+                                               ws0.sflags == sfl && ws0.semis == semis);
+    SurfBufs sb{};
+    if (surf != kSurfNone) {
+      const size_t plane = round256(sizeof(float4) * (size_t)per);
+      sb.n4 = reinterpret_cast<float4*>(ws0.surf.as<char>());
+      sb.b4 = reinterpret_cast<float4*>(ws0.surf.as<char>() + plane);
+      sb.i4 = reinterpret_cast<float4*>(ws0.surf.as<char>() + 2 * plane);
+      sb.e4 = semis ? ws0.surf_e.as<float4>() : nullptr;
+      if (surf == kSurfFill) ws0.svalid = false;  // (until the pass is enqueued)
+      else c->surf_reused += tile_image_pixels(M) * (uint64_t)Fb;
+    }
+    // (a pass whose iteration 0 reads the record with the init folded in launches no k_wave_init: prt_plan.h pass_init)
+    if (pass_init(surf) == Kernel::WaveInit) HIP_TRY(launch_wave_init(Lw, S, A, M, wb, frames));
     for (uint32_t it = 0; it <= iters; it++)
-      HIP_TRY(launch_wave2_iter(Lw, S, A, M, wb, frames, timers ? &c->wt : nullptr, P, lrec, it));
+      HIP_TRY(launch_wave2_iter(Lw, S, A, M, wb, frames, timers ? &c->wt : nullptr, P, lrec, it, surf, &sb));
     if (ws0.wb.pmode == kPrimDense) ws0.pvalid = true;
+    if (surf == kSurfFill) {
+      ws0.sgen = ws0.pgen;
+      ws0.sepoch = c->shade_epoch;
+      ws0.sflags = sfl;
+      ws0.semis = semis;
+      ws0.svalid = true;
+    }
     if (last && want_stats) HIP_TRY(hipEventRecord(c->ev[1], st));
     // post-processing (single-GPU image): the screen pass needs the average and, for the aberration, the
     // accumulator before the last frame
@@ -772,6 +811,19 @@ int prt_shadow_reuse(prt_ctx* c, uint64_t* reused, int32_t reset) {
   }
   HIP_TRY(hipSetDevice(c->device));
   *reused = n;
+  return PRT_OK;
+}
+
+int prt_surface_reuse(prt_ctx* c, uint64_t* reused, int32_t reset) {
+  if (!c || !reused) return fail(PRT_ERR_INVALID_ARGUMENT, "bad surface reuse counter arguments");
+  // host bookkeeping of the calls enqueued so far, as prt_primary_rays: no device counter, no wait
+  uint64_t r = c->surf_reused;
+  if (reset) c->surf_reused = 0;
+  for (prt_ctx* m : c->members) {
+    r += m->surf_reused;
+    if (reset) m->surf_reused = 0;
+  }
+  *reused = r;
   return PRT_OK;
 }
 

@@ -104,6 +104,13 @@ struct WaveState {
   uint64_t pgen = 0, lgen = 0;
   float lpos[18] = {};
   bool lvalid = false;
+  // primary-surface record (SurfBufs: three 16-byte planes in surf, the emission plane in surf_e when some mesh has
+  // an emission texture): valid for the phit it was filled on (sgen, as lgen), for the context's shading epoch
+  // (sepoch) and for the call's normal-map and skybox flags (sflags); semis: it was filled with an emission plane
+  DevBuf surf, surf_e;
+  uint64_t sgen = 0, sepoch = 0;
+  uint32_t sflags = 0;
+  bool semis = false, svalid = false;
 };
 // a frame in flight (prt_set_frames_in_flight): the wavefront chain of one call on its own stream.  Slot 0 uses the
 // context's own wavefront state and frame buffer, the others their own; done = the call's last work (the
@@ -295,6 +302,12 @@ struct prt_ctx {
   // from phit by the calls so far (host bookkeeping, prt_primary_rays)
   uint64_t scene_epoch = 0, inst_epoch = 0;
   uint64_t prim_traced = 0, prim_reused = 0;
+  // primary-surface record (WaveState::surf): shade_epoch counts the calls that change what iteration 0 shades a
+  // fixed primary hit from -- every call that bumps one of the two epochs above, and prt_set_textures, prt_set_sky
+  // and prt_set_instance_materials, which leave the hits alone; surf_reused: items shaded from the record by the calls
+  // so far (host bookkeeping, prt_surface_reuse)
+  uint64_t shade_epoch = 0;
+  uint64_t surf_reused = 0;
   // sharding (prt_shard_init_rccl / prt_shard_attach_rccl / prt_create_group)
   int32_t sh_kind = 0;  // 0 none, 1 RCCL, 2 local group (this context is member 0)
   int32_t sh_rank = 0, sh_world = 1, sh_tile = 32;

@@ -87,6 +87,16 @@ struct WaveBufs {
 };
 static_assert(sizeof(WaveBufs) % 8 == 0 && offsetof(WaveBufs, dead) + 4 == sizeof(WaveBufs),
               "dead fills WaveBufs' tail padding");
+// primary-surface record (prt_shade2.h surf_store; prt_surface.hip): per tile-map entry, indexed like phit and lvis,
+// what the shading of iteration 0 needs of the entry's fixed path-1 primary hit in place of hit_attributes, the hit
+// point and the sky lookup.  SoA planes of 16-byte words, one copy per wavefront state.  A kernel argument of its own
+// behind the k_shade2s forms' Shade2Args, so that WaveBufs and every other kernel's arguments stay where they are
+struct SurfBufs {
+  float4* n4;  // hit: N, t (sign bit: emissive); miss: the sky radiance (or 0), t >= kFar
+  float4* b4;  // m.base, m.rough
+  float4* i4;  // I, m.metal
+  float4* e4;  // m.emis of the entries whose emissive bit is set; null unless some mesh has an emission texture
+};
 #ifdef PRT_LANE_STATS
 void lane_stats_dump();  // diagnostic build: prints and clears the traversal lane counters (prt_wave2.hip)
 #endif
@@ -104,12 +114,18 @@ hipError_t launch_wave_init(const LaunchCfg& c, const SceneDev& S, const TraceAr
 // Pipeline::PlainDeferred: the pass's resolve is one launch behind the last traversal (prt_defer.hip k_resolve_pass).
 // B's rinfo / ne / nb / nk / vis / T then point at plane 0 of `iters` record planes of B.n entries each (plane i at
 // i * B.n); B.R is not used
+// surf: the pass's iteration 0 fills (kSurfFill) or reads (kSurfRead) the primary-surface record R (prt_surface.hip)
 hipError_t launch_wave2_iter(const LaunchCfg& c, const SceneDev& S, const TraceArgs& A, const TileMap& M,
                              const WaveBufs& B, float4* out, WaveTimers* tm, const WavePlan& P, bool lrec,
-                             uint32_t it);
+                             uint32_t it, int surf = kSurfNone, const SurfBufs* R = nullptr);
 // ... whose shading (into the record plane B points at) and resolve launches prt_defer.hip holds
 void launch_shade2d(hipStream_t s, unsigned grid, const SceneDev& S, const TraceArgs& A, const TileMap& M,
                     const WaveBufs& B, uint32_t it, bool i0);
+// iteration 0 of a kPrimReuse pass under the primary-surface record (prt_surface.hip k_shade2s): defer as
+// launch_shade2d's plane, surf kSurfFill, kSurfRead or (deferred) kSurfInit; out: the pass's frame buffer (kSurfInit
+// writes the entries without a pixel, as k_wave_init does)
+void launch_shade2s(hipStream_t s, unsigned grid, const SceneDev& S, const TraceArgs& A, const TileMap& M,
+                    const WaveBufs& B, uint32_t it, bool defer, int surf, const SurfBufs& R, float4* out);
 void launch_resolve_pass(hipStream_t s, unsigned grid, const SceneDev& S, const TraceArgs& A, const WaveBufs& B,
                          uint32_t iters, float4* out, bool learn);
 // zero na words at a and nb words at b (one dispatch)

@@ -20,6 +20,9 @@ constexpr uint32_t kParts = 8;  // XCD parts of a traversal launch's live range,
 constexpr int kMaxIters = 128;  // wavefront iterations per call: bounces <= 64 (AA) / 6 with dielectrics (AA)
 // WaveBufs::pmode
 enum : int32_t { kPrimTrace = 0, kPrimDense = 1, kPrimReuse = 2 };
+// what iteration 0 of a pass does with the primary-surface record (prt_launch.h SurfBufs): nothing, store, shade from
+// it, shade from it and do the wave init's work itself (the pass then launches no k_wave_init)
+enum : int { kSurfNone = 0, kSurfFill = 1, kSurfRead = 2, kSurfInit = 3 };
 
 // A call's work items (pixels x reference frames) index the shadow-queue entries as 4 x item + k in 29 bits
 // (prt_wave2.hip kShIndexMask; the light class takes the top 3), so one pass holds at most 2^27 items; the merged
@@ -35,6 +38,8 @@ struct Tunables {
   uint64_t defer_budget = 4096ull << 20;  // PRT_DEFER_BUDGET_MB (MiB), in bytes: the record planes a pass may take
   bool primary_reuse = true;       // PRT_PRIMARY_REUSE=0: every item's primary ray traced every frame
   bool shadow_reuse = true;        // PRT_SHADOW_REUSE=0: no light-visibility record
+  bool surface_reuse = true;       // PRT_SURFACE_REUSE=0: no primary-surface record
+  bool init_fold = true;           // PRT_INIT_FOLD=0: a pass that shades from that record still launches k_wave_init
   uint32_t dead_shadow = 2;        // PRT_DEAD_SHADOW: 0 traces every shadow ray, 1 skips those whose own contribution
                                    // is zero, unset or anything else (2) also those a zero BRDF value multiplies
   uint64_t max_items = 0;          // PRT_MAX_ITEMS: a smaller pass size, at least 1 (0: unset)
@@ -54,6 +59,8 @@ inline Tunables read_tunables() {
   if (const char* e = std::getenv("PRT_DEFER_BUDGET_MB")) t.defer_budget = std::strtoull(e, nullptr, 10) << 20;
   t.primary_reuse = !off("PRT_PRIMARY_REUSE");
   t.shadow_reuse = !off("PRT_SHADOW_REUSE");
+  t.surface_reuse = !off("PRT_SURFACE_REUSE");
+  t.init_fold = !off("PRT_INIT_FOLD");
   if (const char* e = std::getenv("PRT_DEAD_SHADOW")) {
     const int v = std::atoi(e);
     t.dead_shadow = v == 0 ? 0u : (v == 1 ? 1u : 2u);
@@ -177,6 +184,10 @@ struct WavePlan {
   // dielectrics the misses' pass rewrites hit[item] per item, and the debug modes shade from it: those keep tracing
   // P(0).  The light-visibility record rides on it: wherever it applies, unless switched off alone
   bool preuse = false, lreuse = false;
+  // The primary-surface record rides on both, in the plain pipeline (deferred or not): iteration 0 of a kPrimReuse
+  // pass that holds a light-visibility record fills it, or shades from it once it is valid (surface_form)
+  bool sreuse = false;
+  bool ifold = false;     // ... and a deferred pass that reads it folds the wave init into iteration 0 (kSurfInit)
   uint32_t dead = 2;      // dead shadow rays (prt_wave2.hip nee_live): Tunables::dead_shadow
   bool coop_tail = true;
   bool timeline = false;  // Tunables::debug_queues
@@ -223,6 +234,8 @@ inline int plan_render(int32_t render_mode, uint32_t flags, int32_t bounces, int
                : defer ? Pipeline::PlainDeferred : Pipeline::Plain;
   P.preuse = plain && t.primary_reuse && per > 0 && F > 0;
   P.lreuse = P.preuse && t.shadow_reuse;
+  P.sreuse = P.lreuse && !merge && t.surface_reuse;
+  P.ifold = P.sreuse && defer && t.init_fold;
   P.dead = t.dead_shadow;
   P.coop_tail = t.coop_tail;
   P.timeline = t.debug_queues;
@@ -240,15 +253,30 @@ enum class Kernel {
   Miss2, Miss2Ext, ResMiss2, ResMiss2Ext,                     // k_miss2<EXT>, k_resmiss2<EXT> (misses = 1)
   Shade2, Shade2Learn, Shade2Ext, Shade2Debug,                // k_shade2<false, L>, k_shade2<true>, k_shade2_debug
   Shade2d, Shade2dLearn, Shade2m, Shade2mLearn,               // k_shade2d<L>, k_shade2m<L>
+  Shade2sFill, Shade2sRead, Shade2sdFill, Shade2sdRead,       // k_shade2s<DEFER, SURF> (prt_surface.hip)
+  Shade2sdInit,                                               // k_shade2s<true, kSurfInit>
+  WaveInit,                                                   // k_wave_init (pass_init)
 };
 struct Schedule {
   Kernel trace, resolve, shade;
 };
+// What a pass's iteration 0 does with the primary-surface record: lrec as wave_schedule's, valid: the state's record
+// belongs to its primary hits, the shading epoch and the call's normal-map and skybox flags (prt_api_render.cpp)
+inline int surface_form(const WavePlan& P, bool lrec, bool valid) {
+  if (!P.sreuse || !lrec) return kSurfNone;
+  return valid ? (P.ifold ? kSurfInit : kSurfRead) : kSurfFill;
+}
+// the kernel in front of launch 0 of a pass: k_wave_init, unless iteration 0 does its work (kSurfInit: q0 is then
+// neither written nor read, and the shading counts the items into P(0)'s counters itself)
+inline Kernel pass_init(int surf) { return surf == kSurfInit ? Kernel::None : Kernel::WaveInit; }
 // lrec: the pass runs with kPrimReuse and holds a light-visibility record.  The extension and debug pipelines always
 // trace their primaries (kPrimTrace) and hold no record
-inline Schedule wave_schedule(Pipeline p, bool lrec, int32_t pmode, uint32_t it, uint32_t iters) {
+// surf: surface_form's answer for the pass (the plain pipelines, with lrec)
+inline Schedule wave_schedule(Pipeline p, bool lrec, int32_t pmode, uint32_t it, uint32_t iters, int surf = kSurfNone) {
   const bool plainish = p == Pipeline::Plain || p == Pipeline::PlainDeferred;
   assert(!lrec || pmode == kPrimReuse);
+  assert(surf == kSurfNone || (lrec && plainish));
+  assert(surf != kSurfInit || p == Pipeline::PlainDeferred);
   assert((plainish || p == Pipeline::Merged) || (pmode == kPrimTrace && !lrec));
   const bool learn_res = lrec && it == 1, learn_shade = lrec && it == 0;
   Schedule s{Kernel::Trace2, Kernel::None, Kernel::None};
@@ -260,10 +288,13 @@ inline Schedule wave_schedule(Pipeline p, bool lrec, int32_t pmode, uint32_t it,
     case Pipeline::Plain:
       if (it > 0) s.resolve = learn_res ? Kernel::Res2dLearn : Kernel::Res2d;
       s.shade = learn_shade ? Kernel::Shade2Learn : Kernel::Shade2;
+      if (learn_shade && surf != kSurfNone) s.shade = surf == kSurfRead ? Kernel::Shade2sRead : Kernel::Shade2sFill;
       break;
     case Pipeline::PlainDeferred:  // one resolve per pass, behind the last traversal launch
       if (it == iters) s.resolve = lrec ? Kernel::ResolvePassLearn : Kernel::ResolvePass;
       s.shade = learn_shade ? Kernel::Shade2dLearn : Kernel::Shade2d;
+      if (learn_shade && surf != kSurfNone)
+        s.shade = surf == kSurfInit ? Kernel::Shade2sdInit : surf == kSurfRead ? Kernel::Shade2sdRead : Kernel::Shade2sdFill;
       break;
     case Pipeline::Merged:
       if (it > 0) s.resolve = learn_res ? Kernel::Res2mdLearn : Kernel::Res2md;

@@ -33,13 +33,17 @@ __device__ __noinline__ V3 sample_sky_call(const float* sky, int32_t w, int32_t 
 
 // ---- a segment that misses (:159): the sky radiance (or 0) ends the path, into ne of record e.  rd: the ray's
 // direction where the caller keeps it (a register, or the item's entry of rd, then loaded only under kSkybox)
-__device__ __forceinline__ void shade_miss(const SceneDev& S, const WaveBufs& B, uint32_t fl, size_t e,
-                                           const float4& rd) {
+__device__ __forceinline__ V3 miss_radiance(const SceneDev& S, uint32_t fl, const float4& rd) {
   V3 L = v3(0.0f, 0.0f, 0.0f);
   if (fl & kSkybox) {
     const float4 d = rd;
     L = sample_sky_call(S.sky, S.skyw, S.skyh, v3(d.x, d.y, d.z));
   }
+  return L;
+}
+__device__ __forceinline__ void shade_miss(const SceneDev& S, const WaveBufs& B, uint32_t fl, size_t e,
+                                           const float4& rd) {
+  const V3 L = miss_radiance(S, fl, rd);
   B.ne[e] = make_float4(L.x, L.y, L.z, 0.0f);
 }
 
@@ -165,6 +169,7 @@ __device__ __forceinline__ void queue_live(uint32_t* shq, uint32_t s0, int kind,
 struct Asked {
   bool cached = false;
   uint32_t ask = 0, vis0 = 0, s0 = 0;
+  bool rec = false;  // (cached) a primary-surface record form (below): hp is stored only where a ray is queued
 };
 struct ShadedHit {
   uint32_t rinfo;  // the segment's rinfo bits: status << 16 (kStNeeEnd or kStNeeCont) and kRiEmissive
@@ -173,11 +178,57 @@ struct ShadedHit {
   // the path goes on: ro / rd / info of the item hold the next ray
   __device__ bool cont() const { return ((rinfo >> 16) & 3u) == kStNeeCont; }
 };
-template <bool EXT>
+// The surface of a hit: the hit point and the hit attributes.  shade_hit computes it from the ray and the hit; the
+// primary-surface record keeps the one of a fixed path-1 primary hit (surf_store / surf_load)
+struct Surface {
+  V3 I;
+  HitAttr ha;
+};
+// the emissive term of a hit (:196); all +0 unless the mesh has an emission texture
+__device__ __forceinline__ V3 emission_of(const Material& m) {
+  return v3(0.0f, 0.0f, 0.0f) + v3(1.0f, 1.0f, 1.0f) * m.emis;
+}
+// ---- the primary-surface record (SurfBufs, prt_launch.h; prt_surface.hip): entry r, three 16-byte words.
+//   n4  hit: N, t with the "emissive" bit in its sign (a hit's t is >= 0);  miss: the sky radiance (or 0), t >= kFar
+//   b4  m.base, m.rough           i4  I, m.metal           e4  m.emis, where the emissive bit is set
+// The instance's material kind is not kept: the plain pipeline reads none of it behind hit_attributes (which has folded
+// a mirror into metal and rough already); only the extensions' shading does, and it has no record.
+__device__ __forceinline__ float surf_t(const float4& sn) { return __uint_as_float(__float_as_uint(sn.w) & 0x7FFFFFFFu); }
+__device__ __forceinline__ void surf_store(const SurfBufs& R, uint32_t r, const V3 I, const HitAttr& ha, float t) {
+  const Material& m = ha.m;
+  const V3 em = emission_of(m);
+  const bool emissive = (em.x != 0.0f || em.y != 0.0f || em.z != 0.0f) && R.e4;
+  R.n4[r] = make_float4(ha.N.x, ha.N.y, ha.N.z,
+                        __uint_as_float(__float_as_uint(t) | (emissive ? 0x80000000u : 0u)));
+  R.b4[r] = make_float4(m.base.x, m.base.y, m.base.z, m.rough);
+  R.i4[r] = make_float4(I.x, I.y, I.z, m.metal);
+  if (emissive) R.e4[r] = make_float4(m.emis.x, m.emis.y, m.emis.z, 0.0f);
+}
+// sn, sb, si: the entry's words as the prefetch loaded them
+__device__ __forceinline__ Surface surf_load(const SurfBufs& R, uint32_t r, const float4& sn, const float4& sb,
+                                             const float4& si) {
+  Surface sf;
+  sf.I = v3(si.x, si.y, si.z);
+  sf.ha.N = v3(sn.x, sn.y, sn.z);
+  sf.ha.m.base = v3(sb.x, sb.y, sb.z);
+  sf.ha.m.rough = sb.w;
+  sf.ha.m.metal = si.w;
+  sf.ha.m.emis = v3(0.0f, 0.0f, 0.0f);
+  if (__float_as_uint(sn.w) & 0x80000000u) {
+    const float4 e = R.e4[r];
+    sf.ha.m.emis = v3(e.x, e.y, e.z);
+  }
+  sf.ha.kind = kMatTextured;
+  return sf;
+}
+// SURF (the forms under the primary-surface record, k_shade2s): kSurfFill also stores the surface it computed into
+// entry r of R; kSurfRead enters behind the attributes, with the surface `in` that surf_load rebuilt from the record
+template <bool EXT, int SURF = kSurfNone>
 __device__ __forceinline__ ShadedHit shade_hit(const SceneDev& S, const TraceArgs& A, const WaveBufs& B, uint32_t item,
                                                size_t e, size_t ti, const float4& ro, const float4& rd, float4 hh,
                                                int kind, uint32_t nr, uint32_t info, uint32_t& seed, Asked q,
-                                               uint32_t* shq) {
+                                               uint32_t* shq, const SurfBufs R = {}, uint32_t r = 0,
+                                               const Surface* in = nullptr) {
   const bool cached = q.cached;
   const uint32_t ask = q.ask, vis0 = q.vis0, s0 = q.s0;
   uint32_t live = 0;
@@ -187,9 +238,17 @@ __device__ __forceinline__ ShadedHit shade_hit(const SceneDev& S, const TraceArg
   const float4 o = ro, d = rd;
   const V3 D = v3(d.x, d.y, d.z);
   const uint32_t pk = __float_as_uint(hh.w);
-  const V3 I = v3(o.x, o.y, o.z) + hh.x * D;                                                 // tiny_bvh.h:586
+  V3 I;
+  HitAttr ha;
+  if constexpr (SURF == kSurfRead) {
+    I = in->I;
+    ha = in->ha;
+  } else {
+    I = v3(o.x, o.y, o.z) + hh.x * D;                                                        // tiny_bvh.h:586
+    ha = hit_attributes(S, hit_inst(S, pk), hit_prim(S, pk), hh.y, hh.z, (fl & kNormalMap) != 0);
+  }
+  if constexpr (SURF == kSurfFill) surf_store(R, r, I, ha, hh.x);
   const V3 V = -D;
-  const HitAttr ha = hit_attributes(S, hit_inst(S, pk), hit_prim(S, pk), hh.y, hh.z, (fl & kNormalMap) != 0);
   float4 nk;
   const V3 brdf = nee_lights(S, fl, kind, I, V, ha.N, ha.m, seed, nk, [&](int k, uint32_t light) {
     if (cached && (ask & (1u << (8 * k))))  // compact slots: the asked rays below k come first
@@ -199,9 +258,9 @@ __device__ __forceinline__ ShadedHit shade_hit(const SceneDev& S, const TraceArg
   if (!cached) live = B.dead ? nee_live(S, fl, kind, nk, brdf, B.dead > 1u) : (1u << nr) - 1u;
   // a shadow ray is queued as (light, visibility index) with the segment's hit point I stored once: the traversal
   // kernel rebuilds it (shadow_of, the only reader: a segment that queues no light-class ray needs none)
-  if (cached || live) B.hp[e] = make_float4(I.x, I.y, I.z, 0.0f);
+  if ((cached && (!q.rec || ask)) || live) B.hp[e] = make_float4(I.x, I.y, I.z, 0.0f);
   uint32_t emissive = 0;
-  const V3 em = v3(0.0f, 0.0f, 0.0f) + v3(1.0f, 1.0f, 1.0f) * ha.m.emis;                    // :196
+  const V3 em = emission_of(ha.m);                                                           // :196
   if (em.x != 0.0f || em.y != 0.0f || em.z != 0.0f) {  // otherwise em is +0 and the resolve rebuilds it
     B.ne[e] = make_float4(em.x, em.y, em.z, 0.0f);
     emissive = kRiEmissive;
@@ -277,11 +336,21 @@ typedef const __attribute__((address_space(4))) Shade2Args* Shade2ArgsPtr;
 // DEFER (plain form): a pass with a deferred resolve (prt_defer.hip k_shade2d / k_resolve_pass).  The host hands the
 // launch the record plane of its iteration in rinfo / ne / nb / nk / vis / T, so the one index that differs is the
 // throughput's: the plane holds one entry per item, not one per depth.
-template <bool EXT, bool I0, bool DEFER>
+// SURF (I0 forms; prt_surface.hip k_shade2s): kSurfFill stores each item's surface (or its sky radiance) into the
+// primary-surface record R as it shades it, kSurfRead shades from the record: its prefetch loads the entry and never
+// touches phit, the ShadeTri records, the texels, the sRGB table, the sky or the descriptors.  The stored values are
+// the ones the fill form just used, so both forms run the rest of shade_hit on the same bits.
+// kSurfInit: kSurfRead without a k_wave_init in front of it.  It walks the pass's items by index as k_wave_init does
+// (item_pixel, the `out` entry and rinfo 0 of an entry without a pixel), computes the seed, the jitter and the
+// primary ray with k_wave_init's own functions, writes seed, jit, s1 and rinfo itself and counts the items into P(0)'s
+// counters; q0, info, ro and rd of the wave init are neither written nor read
+template <bool EXT, bool I0, bool DEFER, int SURF = kSurfNone>
 __device__ __forceinline__ void shade2_body(const SceneDev& S, const TraceArgs& A, const TileMap& M, const WaveBufs& B,
-                                            uint32_t iter) {
+                                            uint32_t iter, const SurfBufs R = {}, float4* __restrict__ out = nullptr) {
+  constexpr bool kRead = SURF == kSurfRead || SURF == kSurfInit;
   static_assert(!(EXT && I0), "the light-visibility record belongs to the plain pipelines");
   static_assert(!(EXT && DEFER), "the deferred resolve belongs to the plain pipeline");
+  static_assert(SURF == kSurfNone || I0, "the primary-surface record rides on the light-visibility record");
   const Shade2ArgsPtr args = (Shade2ArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
   // fail the call if the Shade2Args layout does not match this compiler's, or the block is not kBlock threads.  The
   // block-size test also makes blockDim.x a constant for the appends below: read anew inside the chunk loop (a vector
@@ -298,7 +367,10 @@ __device__ __forceinline__ void shade2_body(const SceneDev& S, const TraceArgs& 
   uint32_t* shcnt = qcounter(B.ctr, iter, 1, sub);
   uint32_t* ncnt = qcounter(B.ctr, iter + 1, 0, sub);
   uint32_t* shq = B.shq + (size_t)sub * B.scap;
-  const uint32_t total = load_prefix(B.ctr, iter, 0, pref);
+  uint32_t total_;
+  if constexpr (SURF == kSurfInit) total_ = B.n;
+  else total_ = load_prefix(B.ctr, iter, 0, pref);
+  const uint32_t total = total_;
   const uint32_t fl = A.flags;
   // software pipeline over the grid-stride chunks: the next chunk's item, info, hit and seed are loaded while this
   // chunk's item is shaded
@@ -306,11 +378,27 @@ __device__ __forceinline__ void shade2_body(const SceneDev& S, const TraceArgs& 
   float4 hh_n = make_float4(kFar, 0.0f, 0.0f, 0.0f);
   float4 ro_n = make_float4(0.0f, 0.0f, 0.0f, 0.0f), rd_n = ro_n;  // (plain form: the ray too)
   uint2 lv_n = make_uint2(0u, 0u);                                 // (I0: the entry's light-visibility bytes)
+  float4 sn_n = ro_n, sb_n = ro_n, si_n = ro_n;                    // (kSurfRead: the entry's three record words)
   auto prefetch = [&](uint32_t cc) {
     const uint32_t gg = cc * kBlock + threadIdx.x;
     if (gg < total) {
+      if constexpr (SURF == kSurfInit) {  // item gg itself: the record and the light visibility of its entry
+        const uint32_t r = (B.base + gg) % B.pitems;
+        item_n = gg;
+        sn_n = R.n4[r]; sb_n = R.b4[r]; si_n = R.i4[r];
+        lv_n = B.lvis[r];
+        return;
+      }
       item_n = q[map_slot(pref, gg, B.qcap)];
       info_n = B.info[item_n];
+      if constexpr (SURF == kSurfRead) {  // the record in place of the hit; of the ray, the direction alone
+        const uint32_t r = (B.base + item_n) % B.pitems;
+        sn_n = R.n4[r]; sb_n = R.b4[r]; si_n = R.i4[r];
+        lv_n = B.lvis[r];
+        seed_n = B.seed[item_n];
+        rd_n = B.rd[item_n];
+        return;
+      }
       // iteration 0 with primary-hit reuse (plain form only): the hit of the pixel's fixed path-1 primary ray
       hh_n = (!EXT && iter == 0 && B.pmode != kPrimTrace) ? B.phit[(B.base + item_n) % B.pitems] : B.hit[item_n];
       if constexpr (I0) lv_n = B.lvis[(B.base + item_n) % B.pitems];
@@ -319,6 +407,7 @@ __device__ __forceinline__ void shade2_body(const SceneDev& S, const TraceArgs& 
     }
   };
   prefetch(blockIdx.x);
+  uint32_t init_count = 0;  // (kSurfInit) the items this wave found a pixel for
   for (uint32_t c = blockIdx.x; c * kBlock < total; c += gridDim.x) {
     const float4 ro_c = ro_n, rd_c = rd_n;
     // The scene and buffer descriptors are read from the kernarg segment inside each chunk (scalar loads, scalar
@@ -334,13 +423,55 @@ __device__ __forceinline__ void shade2_body(const SceneDev& S, const TraceArgs& 
     q.cached = I0;
     int kind = 0;
     float4 hh = make_float4(kFar, 0.0f, 0.0f, 0.0f);
-    const bool active = g < total;
+    // (kSurfInit) k_wave_init's work for item g: its pixel, seed, jitter and primary ray direction
+    bool init_valid = false;
+    uint32_t init_seed_ = 0;
+    float4 init_rd = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if constexpr (SURF == kSurfInit) {
+      if (g < total) {
+        const uint32_t gi = Bc.base + g;  // item index within the call
+        const uint32_t f = gi / M.items, r = gi % M.items;
+        int32_t x, y;
+        init_valid = item_pixel(M, r, x, y);
+        if (init_valid) {
+          const uint32_t p = (uint32_t)(y * A.W + x);
+          init_seed_ = init_seed(A.seed + p + (uint32_t)A.W * (uint32_t)A.H * (A.frame_index + f));
+          float jx = 0.0f, jy = 0.0f;
+          if (A.flags & kAA) { jx = random_float(init_seed_); jy = random_float(init_seed_); }  // :61
+          const Ray r1 = primary_ray(Sc, (float)x, (float)y, A.W, A.H);
+          init_rd = make_float4(r1.D.x, r1.D.y, r1.D.z, 0.0f);
+          Bc.jit[g] = make_float2(jx, jy);
+        } else {
+          out[g] = make_float4(0.0f, 0.0f, 0.0f, kFar);
+          Bc.rinfo[g] = 0u;
+        }
+      }
+      init_count += (uint32_t)__popcll(__ballot(init_valid));
+    }
+    const float4 rd_s = SURF == kSurfInit ? init_rd : rd_c;
+    const bool active = SURF == kSurfInit ? init_valid : g < total;
+    const float4 sn = sn_n, sb = sb_n, si = si_n;
     if (active) {
       item = item_n; info = info_n; hh = hh_n;
-      const uint32_t sd = seed_n;
+      if constexpr (kRead) hh.x = surf_t(sn);
+      const uint32_t sd = SURF == kSurfInit ? init_seed_ : seed_n;
       const uint2 lv = lv_n;
-      if ((info & 0x1FFu) == 0) Bc.s1[item].w = hh.x;                                        // r1.hit.t
-      if (!EXT && hh.x >= kFar) shade_miss(Sc, Bc, fl, item, rd_c);
+      if constexpr (SURF == kSurfInit) Bc.s1[item] = make_float4(0.0f, 0.0f, 0.0f, hh.x);
+      else if ((info & 0x1FFu) == 0) Bc.s1[item].w = hh.x;                                   // r1.hit.t
+      if constexpr (kRead) {
+        if (hh.x >= kFar) {
+          Bc.ne[item] = make_float4(sn.x, sn.y, sn.z, 0.0f);
+          if constexpr (SURF == kSurfInit) Bc.seed[item] = sd;  // (a hit's seed is stored by shade_hit)
+        }
+      } else if constexpr (SURF == kSurfFill) {
+        if (hh.x >= kFar) {
+          const V3 L = miss_radiance(Sc, fl, rd_c);
+          Bc.ne[item] = make_float4(L.x, L.y, L.z, 0.0f);
+          R.n4[(Bc.base + item) % Bc.pitems] = make_float4(L.x, L.y, L.z, hh.x);
+        }
+      } else {
+        if (!EXT && hh.x >= kFar) shade_miss(Sc, Bc, fl, item, rd_c);
+      }
       if (hh.x < kFar) {
         seed = sd;
         kind = nee_kind(fl, seed);                                                           // :198-214
@@ -356,7 +487,17 @@ __device__ __forceinline__ void shade2_body(const SceneDev& S, const TraceArgs& 
                                nr - (uint32_t)__popc(q.ask), sm);
     const uint32_t depth = info & 0xFFu, path = (info >> 8) & 1u;
     ShadedHit h = {kStMiss << 16, 0u, false};
-    if (nr)
+    if constexpr (SURF != kSurfNone) {
+      q.rec = true;
+      if (nr) {
+        const uint32_t r = (Bc.base + item) % Bc.pitems;
+        Surface sf;
+        if constexpr (kRead) sf = surf_load(R, r, sn, sb, si);
+        h = shade_hit<EXT, kRead ? kSurfRead : SURF>(Sc, A, Bc, item, item,
+                                                     DEFER ? (size_t)item : (size_t)depth * Bc.n + item, ro_c, rd_s, hh,
+                                                     kind, nr, info, seed, q, shq, R, r, &sf);
+      }
+    } else if (nr)
       h = shade_hit<EXT>(Sc, A, Bc, item, item, DEFER ? (size_t)item : (size_t)depth * Bc.n + item,
                          EXT ? Bc.ro[item] : ro_c, EXT ? Bc.rd[item] : rd_c, hh, kind, nr, info, seed, q, shq);
     if constexpr (!I0) {  // only the mask lived across the NEE block: the live rays' slots, the dead ones counted
@@ -379,6 +520,10 @@ __device__ __forceinline__ void shade2_body(const SceneDev& S, const TraceArgs& 
     }
     const uint32_t slot = block_append(ncnt, next ? 1u : 0u, sm);
     if (next) qn[sub * Bc.qcap + slot] = item;
+  }
+  // (kSurfInit) P(0)'s count, which k_wave_init's appends would have produced: the ray totals are the queue counters
+  if constexpr (SURF == kSurfInit) {
+    if (lane_id() == 0 && init_count) atomicAdd(qcounter(B.ctr, 0, 0, sub), init_count);
   }
 }
 // EXT: held to 3 waves/SIMD (168 VGPRs, no spills; unbounded it took 175 and ran 2 waves: C5 frame 135.7 ->

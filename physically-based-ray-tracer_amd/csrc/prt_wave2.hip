@@ -645,7 +645,7 @@ __host__ inline unsigned producer_blocks(const LaunchCfg& c) {
 // (prt_plan.h) names for the plan's pipeline
 hipError_t launch_wave2_iter(const LaunchCfg& c, const SceneDev& S, const TraceArgs& A, const TileMap& M,
                              const WaveBufs& B, float4* out, WaveTimers* tm, const WavePlan& P, bool lrec,
-                             uint32_t it) {
+                             uint32_t it, int surf, const SurfBufs* R) {
   if (B.n == 0) return hipSuccess;
   const unsigned gprod = producer_blocks(c);
   // k_shade2 over 4x the resident blocks when a call holds >= 2^21 items: the extra blocks queue behind the
@@ -660,7 +660,7 @@ hipError_t launch_wave2_iter(const LaunchCfg& c, const SceneDev& S, const TraceA
   const unsigned gshade = PRT_SHADE_GRID;
 #endif
   const uint32_t iters = P.iters;
-  const Schedule k = wave_schedule(P.pipeline, lrec, B.pmode, it, iters);
+  const Schedule k = wave_schedule(P.pipeline, lrec, B.pmode, it, iters, surf);
   if (tm) (void)hipEventRecord(tm->ev[4 * it + 0], c.stream);
   // deferred resolve (prt_defer.hip): B's record pointers are plane 0.  This launch's shading gets plane `it`; its
   // traversal gets vis of plane it - 1, whose bytes the shadow entries of S(it - 1) index (shadow_vis)
@@ -708,6 +708,12 @@ hipError_t launch_wave2_iter(const LaunchCfg& c, const SceneDev& S, const TraceA
     case Kernel::Shade2d: launch_shade2d(c.stream, gshade, S, A, M, Bs, it, false); break;
     case Kernel::Shade2Learn: PRT_LAUNCH((k_shade2<false, true>), gshade, S, A, M, B, it); break;
     case Kernel::Shade2: PRT_LAUNCH(k_shade2<false>, gshade, S, A, M, B, it); break;
+    // iteration 0 under the primary-surface record (prt_surface.hip)
+    case Kernel::Shade2sdFill: launch_shade2s(c.stream, gshade, S, A, M, Bs, it, true, kSurfFill, *R, out); break;
+    case Kernel::Shade2sdRead: launch_shade2s(c.stream, gshade, S, A, M, Bs, it, true, kSurfRead, *R, out); break;
+    case Kernel::Shade2sdInit: launch_shade2s(c.stream, gshade, S, A, M, Bs, it, true, kSurfInit, *R, out); break;
+    case Kernel::Shade2sFill: launch_shade2s(c.stream, gshade, S, A, M, B, it, false, kSurfFill, *R, out); break;
+    case Kernel::Shade2sRead: launch_shade2s(c.stream, gshade, S, A, M, B, it, false, kSurfRead, *R, out); break;
     default: assert(k.shade == Kernel::None);
   }
 #undef PRT_LAUNCH

@@ -34,7 +34,7 @@ EXPORTS = [
     "prt_save_accumulation", "prt_load_accumulation", "prt_ray_totals", "prt_set_frames_in_flight", "prt_finish",
     "prt_render_aov", "prt_denoise_defaults", "prt_denoise", "prt_denoise_timings",
     "prt_reproject_defaults", "prt_reproject", "prt_primary_rays", "prt_shadow_reuse",
-    "prt_shadow_dead",
+    "prt_shadow_dead", "prt_surface_reuse",
     "prt_render_aov_ids", "prt_instance_motion", "prt_reproject_motion",
     "prt_temporal_defaults", "prt_reproject_moments", "prt_denoise_variance_defaults", "prt_denoise_variance",
     "prt_update_mesh", "prt_read_blas", "prt_read_blas_tris",
@@ -208,6 +208,7 @@ def load():
         "prt_primary_rays": ([vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int32], C.c_int),
         "prt_shadow_reuse": ([vp, C.POINTER(C.c_uint64), C.c_int32], C.c_int),
         "prt_shadow_dead": ([vp, C.POINTER(C.c_uint64), C.c_int32], C.c_int),
+        "prt_surface_reuse": ([vp, C.POINTER(C.c_uint64), C.c_int32], C.c_int),
         "prt_tile_buffer_pixels": ([i32, i32, i32, i32, C.POINTER(C.c_int64)], C.c_int),
         "prt_tile_pixel_map": ([i32, i32, i32, i32, i32, C.c_void_p], C.c_int),
         "prt_render_tiles": ([vp, C.POINTER(RenderParams), i32, i32, i32, vp, C.POINTER(Stats)], C.c_int),

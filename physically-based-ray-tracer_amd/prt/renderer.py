@@ -604,6 +604,16 @@ class Context:
         check(self.L.prt_shadow_reuse(self.h, C.byref(n), 1 if reset else 0))
         return int(n.value)
 
+    def surface_reuse(self, reset=False):
+        """Work items (pixels x reference frames) whose path-1 primary hit the calls so far shaded from the kept
+        surface values -- normal, material, hit point, or a miss's sky radiance -- instead of gathering them again
+        (prt_surface_reuse).  A host counter, no wait.  0 outside the plain pipeline, with PRT_SURFACE_REUSE=0,
+        PRT_SHADOW_REUSE=0 or PRT_PRIMARY_REUSE=0, and in the first two calls of a view (the first traces the primary
+        hits, the second fills the record)."""
+        n = C.c_uint64()
+        check(self.L.prt_surface_reuse(self.h, C.byref(n), 1 if reset else 0))
+        return int(n.value)
+
     def shadow_dead(self, reset=False):
         """Shadow rays the calls so far counted instead of tracing because their contribution is exactly zero: the
         light behind the shading normal, the hit outside the spot's cone, a black light, PRT_FLAG_LIGHTED off

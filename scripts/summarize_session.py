@@ -5,7 +5,8 @@ profiles/<tag>_<scene>_prof.json, profiles/<tag>_<scene>_kernel_stats.csv and pr
 
 Per kernel:
 - calls / avg_ns / min_ns / max_ns: the --kernel-trace --stats pass;
-- launches_per_frame: dispatches of the kernel / dispatches of k_wave_init (once per frame) in the same pass;
+- launches_per_frame: dispatches of the kernel / dispatches of k_accumulate (once per frame; k_wave_init is not: a
+  frame whose iteration 0 folds the init in launches none) in the same pass;
 - hbm_*_bytes_per_launch: FETCH_SIZE x 2 x 1024 + WRITE_SIZE x 1024 (MI355X_MICROARCH.md HBM section, gfx950
   FETCH_SIZE correction; checked for this kernel's access shapes in profiles/fetch_calibration.json), each from its
   own pass; hbm_bytes_per_frame = per launch x launches_per_frame;
@@ -62,7 +63,7 @@ def main():
         if not os.path.exists(f):
             continue
         means, calls, _ = pass_means(f)
-        init = next((n for k2, n in calls.items() if k2.endswith("k_wave_init")), None)
+        init = next((n for k2, n in calls.items() if k2.endswith("k_accumulate")), None)
         for k, d in means.items():
             r = K.setdefault(k, {})
             r[f"{counter}_raw_kib_per_launch"] = d[counter]
