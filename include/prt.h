@@ -328,7 +328,8 @@ int prt_set_instance_materials(prt_ctx* ctx, const int32_t* kinds, int32_t count
  * node j gets the box of instance slot[8j + s], an interior slot its child node's uninflated box, and every node is
  * re-encoded bottom-up on the device, one launch per tree level.  A refit with the transforms the tree was built for
  * reproduces the built bytes; updating to T' and back to T is byte-identical as well.  When to pay for a fresh SAH
- * tree is the caller's decision: prt_tlas_cost measures the tree as it stands, prt_set_instances is the rebuild.
+ * tree is the caller's decision: prt_tlas_cost measures the tree as it stands; prt_rebuild_instances (on the device)
+ * and prt_set_instances (on the host) are the rebuilds.
  * in_flags = 0: host memory, copied before the call returns and uploaded in the context stream's order.  On a local
  * group or RCCL context it applies to every member.
  * in_flags = PRT_IN_DEVICE: device memory on the context's device, 16-byte aligned, read by one kernel in the context
@@ -349,6 +350,51 @@ int prt_set_instance_materials(prt_ctx* ctx, const int32_t* kinds, int32_t count
  * memory: PRT_ERR_INVALID_ARGUMENT.  No meshes or no instances yet: PRT_ERR_NOT_READY.  A worker build that failed
  * earlier is reported as prt_set_instances reports it.  Nothing changes in any of these cases. */
 int prt_update_instances(prt_ctx* ctx, const float* transforms, int32_t count, uint32_t in_flags);
+/* prt_update_instances with a fresh device build of the instance BVH in place of the refit (additive in ABI 10;
+ * DESIGN.md 8 "Instance rebuild"; the definitions: csrc/prt_tlas_build.h).  It stands to prt_update_instances as
+ * prt_rebuild_mesh stands to prt_update_mesh: the way to pay for a fresh tree when prt_tlas_cost has grown, also while
+ * the transforms are device-resident and the library holds no host copy for prt_set_instances.
+ * transforms != NULL: the arguments, the PRT_IN_DEVICE rule, the alignment rule, the local-group rule and the
+ * resulting host / device-resident state are prt_update_instances'.  transforms = NULL: the instances stay where they
+ * are -- in the device-resident state the transforms kept on the device are used, otherwise the host's; count must
+ * still equal the instance count and in_flags must be 0.
+ * builder: PRT_BUILDER_GPU_LBVH or PRT_BUILDER_GPU_PLOC (treelet passes: the builders' defaults, PRT_TRBVH, as at
+ * prt_rebuild_mesh); the host builders return PRT_ERR_UNSUPPORTED (prt_set_instances is their rebuild), any other
+ * value PRT_ERR_INVALID_ARGUMENT.  On the linear list (at most 64 instances without PRT_TLAS=1) the call is exactly
+ * prt_update_instances, with transforms = NULL a no-op that returns PRT_OK; builder is still validated.
+ * The contract: afterwards every query, render and AOV returns, bit for bit, what a fresh context returns after
+ * prt_set_instances with these transforms and the same mesh indices and material kinds: hits do not depend on the
+ * tree.  prt_stats.stack_overflows stays 0.  prt_read_tlas returns a tree in the host build's form: every instance in
+ * exactly one leaf slot, with count 1; tri_base = 8j in node j; 0xFFFFFFFF in the slot table wherever a slot is no
+ * leaf slot; interior children consecutive from child_base, with larger indices than their parent; each level's
+ * nodes contiguous.  The node bytes are what the refit of prt_update_instances (csrc/prt_tlas_refit.h refit_tlas8)
+ * makes of the same topology over the same instance boxes: the device collapse encodes as the refit does.  The tree is
+ * the same from host memory, device memory and NULL for the same transforms and builder, and two rebuilds of the same
+ * state with the same builder give the same bytes: the builder's collapse hands out node positions by atomic
+ * counters, and the commit puts every level into its canonical order (the children of a level's nodes in those
+ * nodes' order, each node's in slot order).
+ * Afterwards a prt_update_instances refits the new topology and a prt_set_instances behaves as before;
+ * prt_scene_info.tlas_rebuilds and tlas_async, which count worker builds, do not move.
+ * Failure: the tree is built into scratch the context keeps (176 bytes per instance: 48 of builder input, 80 of
+ * nodes, 48 of records; sized at the first rebuild of an instance count, and only that call may allocate) and
+ * committed to the next copy of the instance state only after the build succeeded.  A failed build returns
+ * PRT_ERR_HIP; a tree that with the deepest BLAS would exceed 64 levels returns PRT_ERR_UNSUPPORTED; in both cases
+ * the live instances, tree and host / device-resident state are as before.  A tree deeper than the levels the
+ * traversal stacks were sized for (prt_scene_info.tlas_depth) raises that figure to its depth: the stacks are sized
+ * at every launch, and a deeper stack can cost an occupancy step.
+ * Ordering: like prt_update_instances the call does not join the frames in flight and writes the next copy of the
+ * instance state once the context stream has waited for the frames that read it; frames enqueued before the call see
+ * the old instances, frames enqueued after it the new tree.  Unlike prt_update_instances it blocks the host: the
+ * builder synchronises the context stream once per PLOC iteration and once per tree level, so the call also waits
+ * for the work queued on that stream before it (on an RCCL context with the bounded wait).
+ * Transforms are not checked for finiteness: with a non-finite one the call either builds a traversable tree or
+ * returns an error with nothing changed; which of the two is outside the contract.
+ * NULL context, count different from the instance count, unknown flag bits, flags without transforms, misaligned
+ * device memory: PRT_ERR_INVALID_ARGUMENT.  No meshes or no instances yet: PRT_ERR_NOT_READY.  Device transforms on a
+ * local group: PRT_ERR_UNSUPPORTED.  A worker build that failed earlier is reported as prt_update_instances reports
+ * it.  Nothing changes in any of these cases.  On a local group or RCCL context a host-memory or NULL call applies
+ * to every member. */
+int prt_rebuild_instances(prt_ctx* ctx, const float* transforms, int32_t count, uint32_t in_flags, int32_t builder);
 /* prt_blas_cost's measure (csrc/prt_blas_cost.h) of the instance BVH as it stands on the device; a leaf slot counts
  * one instance.  0 when the rays walk the linear list.  The same two kernels, no atomics: two calls return the same
  * bits.  The call joins the frames in flight and waits on the host once, for the 8 bytes of the result.  The library

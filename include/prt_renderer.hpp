@@ -183,6 +183,13 @@ class Scene {
     for (const GameObject& g : gameobjects) xf.insert(xf.end(), g.transform.begin(), g.transform.end());
     check(prt_update_instances(ctx, xf.data(), (int32_t)gameobjects.size(), 0u));
   }
+  // the same with a fresh device build of the instance BVH in place of the refit (prt_rebuild_instances; builder:
+  // PRT_BUILDER_GPU_LBVH or PRT_BUILDER_GPU_PLOC)
+  void RebuildInstances(prt_ctx* ctx, int32_t builder = PRT_BUILDER_GPU_PLOC) const {
+    std::vector<float> xf;
+    for (const GameObject& g : gameobjects) xf.insert(xf.end(), g.transform.begin(), g.transform.end());
+    check(prt_rebuild_instances(ctx, xf.data(), (int32_t)gameobjects.size(), 0u, builder));
+  }
 };
 
 // Camera (Core/Camera.h:11-31): position, target, the screen plane GetPrimaryRay interpolates, its basis
@@ -343,8 +350,8 @@ class Renderer {
   // restarts in full.  InstancesMovedDevice takes the transforms from device memory instead (16 floats per game
   // object, 16-byte aligned, read in the context stream's order); scene.gameobjects then no longer says where the
   // objects are.  TlasCost() is the SAH cost of the instance BVH as it stands (prt_tlas_cost): it grows while the refit
-  // follows the objects away from where the tree was built; scene.UploadInstances(ctx) builds a fresh tree.  When
-  // to rebuild is the caller's decision.
+  // follows the objects away from where the tree was built; scene.UploadInstances(ctx) builds a fresh tree on the host, InstancesRebuilt /
+  // InstancesRebuiltDevice one on the device.  When to rebuild is the caller's decision.
   void InstancesMoved() {
     scene.UpdateInstances(ctx_);
     check(prt_reset_accumulation(ctx_, 1));
@@ -357,6 +364,18 @@ class Renderer {
     double v = 0.0;
     check(prt_tlas_cost(ctx_, &v));
     return v;
+  }
+  // TlasCost() has grown: a fresh device build of the instance BVH (prt_rebuild_instances), over scene.gameobjects,
+  // over transforms in device memory, or (InstancesRebuiltDevice(nullptr)) over the instances where they are -- also while
+  // the transforms are device-resident.  Blocks until the builder is through; the accumulation restarts in full.
+  void InstancesRebuilt(int32_t builder = PRT_BUILDER_GPU_PLOC) {
+    scene.RebuildInstances(ctx_, builder);
+    check(prt_reset_accumulation(ctx_, 1));
+  }
+  void InstancesRebuiltDevice(const float* transforms_dev, int32_t builder = PRT_BUILDER_GPU_PLOC) {
+    check(prt_rebuild_instances(ctx_, transforms_dev, (int32_t)scene.gameobjects.size(), transforms_dev ? PRT_IN_DEVICE : 0u,
+                                builder));
+    check(prt_reset_accumulation(ctx_, 1));
   }
 
   // The SAH cost of model index's BLAS as it stands (prt_blas_cost): it grows while ModelChanged / SkinModel refit

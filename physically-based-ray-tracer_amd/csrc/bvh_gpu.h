@@ -14,6 +14,7 @@ struct GpuBlasInfo {
   uint32_t leaves;  // leaf children
   int32_t depth;    // wide-tree levels
   float bmin[3], bmax[3];  // exact root bounds
+  uint32_t syncs;   // times the build waited for the stream on the host (PLOC iterations, tree levels, ...)
 };
 
 // tri_dev: fat triangles float4 x 3T in device memory.  nodes_out: room for T Node8; tris_out: T TriMT.

@@ -757,6 +757,7 @@ hipError_t gpu_build_blas8(hipStream_t s, const float* tri_dev, int32_t n_tris, 
                            int trbvh, int ploc_radius) {
   const int n = n_tris;
   if (n <= 0) return hipErrorInvalidValue;
+  uint32_t syncs = 0;  // host waits for the stream (GpuBlasInfo::syncs)
   const size_t nn = 2 * (size_t)n - 1;
   // scratch: keys x2, left/right/parent/first/count/flag, boxes, two task arrays, counters
   unsigned long long *keys = nullptr, *keys2 = nullptr;
@@ -822,12 +823,12 @@ hipError_t gpu_build_blas8(hipStream_t s, const float* tri_dev, int32_t n_tris, 
                          keep, ctr, dp, n, max_leaf);
       if ((err = hipcub::DeviceSelect::Flagged(stmp, stmp_bytes, clus2, keep, clus, nsel, m, s))) break;
       int mm = 0;
-      if ((err = hipMemcpyAsync(&mm, nsel, 4, hipMemcpyDeviceToHost, s)) || (err = hipStreamSynchronize(s))) break;
+      if ((err = hipMemcpyAsync(&mm, nsel, 4, hipMemcpyDeviceToHost, s)) || (err = (syncs++, hipStreamSynchronize(s)))) break;
       if (mm >= m) err = hipErrorInvalidValue;  // no merge: cannot happen (the best pair is always mutual)
       m = mm;
     }
     uint32_t c[4];
-    if (!err && !(err = hipMemcpyAsync(c, ctr, 16, hipMemcpyDeviceToHost, s)) && !(err = hipStreamSynchronize(s)) &&
+    if (!err && !(err = hipMemcpyAsync(c, ctr, 16, hipMemcpyDeviceToHost, s)) && !(err = (syncs++, hipStreamSynchronize(s))) &&
         (c[0] != 0u || (c[3] & 0x80000000u)))
       err = hipErrorInvalidValue;  // not exactly n - 1 internal nodes
     pfree();
@@ -868,7 +869,7 @@ hipError_t gpu_build_blas8(hipStream_t s, const float* tri_dev, int32_t n_tris, 
       hipLaunchKernelGGL(k_dp_rebuild, dim3(grid_of(n)), dim3(kB), 0, s, n, left, right, parent, box, count, flag, dp,
                          max_leaf, terr);
     uint32_t te = 0;
-    if (!err && !(err = hipMemcpyAsync(&te, terr, 4, hipMemcpyDeviceToHost, s)) && !(err = hipStreamSynchronize(s)) &&
+    if (!err && !(err = hipMemcpyAsync(&te, terr, 4, hipMemcpyDeviceToHost, s)) && !(err = (syncs++, hipStreamSynchronize(s))) &&
         te != 0u)
       err = hipErrorInvalidValue;  // malformed tree
     tfree();
@@ -892,7 +893,7 @@ hipError_t gpu_build_blas8(hipStream_t s, const float* tri_dev, int32_t n_tris, 
                        count, max_leaf, ta, ntasks, tb, ctr, nodes_out, tris_out, dp);
     if ((err = hipGetLastError())) return fail(err);
     uint32_t c[4];
-    if ((err = hipMemcpyAsync(c, ctr, 16, hipMemcpyDeviceToHost, s)) || (err = hipStreamSynchronize(s)))
+    if ((err = hipMemcpyAsync(c, ctr, 16, hipMemcpyDeviceToHost, s)) || (err = (syncs++, hipStreamSynchronize(s))))
       return fail(err);
     if (c[3] & 0x80000000u) return fail(hipErrorInvalidValue);  // malformed tree (bounds checks above)
     ntasks = c[2];
@@ -905,8 +906,9 @@ hipError_t gpu_build_blas8(hipStream_t s, const float* tri_dev, int32_t n_tris, 
   info->depth = (int32_t)depth;
   if (info->tris != (uint32_t)n) return fail(hipErrorInvalidValue);
   float rb[6];
-  if ((err = hipMemcpyAsync(rb, box, 24, hipMemcpyDeviceToHost, s)) || (err = hipStreamSynchronize(s))) return fail(err);
+  if ((err = hipMemcpyAsync(rb, box, 24, hipMemcpyDeviceToHost, s)) || (err = (syncs++, hipStreamSynchronize(s)))) return fail(err);
   for (int k = 0; k < 3; k++) { info->bmin[k] = rb[k]; info->bmax[k] = rb[3 + k]; }
+  info->syncs = syncs;
   return fail(hipSuccess);
 }
 

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -16,6 +17,7 @@
 #include <vector>
 
 #include "bvh_build.h"
+#include "bvh_gpu.h"
 #include "prt_blas_cost_gpu.h"
 #include "prt_ctx.h"
 #include "prt_deform.h"
@@ -198,13 +200,14 @@ int prt::host::stage_release(prt_ctx*, StageSlot& st, hipStream_t s) {
 
 namespace {
 
-// the refit input of every instance (prt_refit.h) from the host's transforms, mesh boxes and kinds
-void fill_inst_src(const prt_ctx* c, InstSrc* src) {
+// the refit input of every instance (prt_refit.h) from host transforms xf (16 floats each: the host's inst_xf, or a
+// call's own before it commits them), the mesh boxes and the kinds
+void fill_inst_src(const prt_ctx* c, const float* xf, InstSrc* src) {
   const int32_t n = (int32_t)c->inst_mesh.size();
   for (int32_t i = 0; i < n; i++) {
     InstSrc& s = src[i];
     const uint32_t m = c->inst_mesh[i];
-    std::memcpy(s.T, &c->inst_xf[16 * (size_t)i], sizeof(s.T));
+    std::memcpy(s.T, xf + 16 * (size_t)i, sizeof(s.T));
     const MeshHost& mh = c->mesh_info[m];
     std::memcpy(s.bmin, mh.bmin, sizeof(s.bmin));
     std::memcpy(s.bmax, mh.bmax, sizeof(s.bmax));
@@ -305,28 +308,25 @@ int tlas_topology(prt_ctx* c, int32_t n) {
   return PRT_OK;
 }
 
-// prt_update_instances and, while the transforms are device-resident, every refresh of the instance records: the
-// next copy of the instance state from new transforms (or from the same ones under new kinds or mesh boxes), with the
-// instance BVH refitted over it (prt_tlas_refit.h).  xf_dev: packed 4x4 matrices in device memory; null: the host's
-// inst_xf, or, while prt_ctx::xf_device, the transforms kept in the current copy's inst_src.  Everything is enqueued on
-// the context stream: no host build, no worker job, no wait for the GPU.
-int refit_instances(prt_ctx* c, const float* xf_dev) {
+// What prt_update_instances and prt_rebuild_instances share: the records of the next copy of the instance state
+// (isets[nx]: inst_src, then inst by k_refit) from new transforms, or from the same ones under new kinds or mesh boxes,
+// once the context stream has waited for the frames that read that copy.  xf_host: 16 floats per instance in host
+// memory; xf_dev: packed 4x4 matrices in device memory; both null: the transforms kept in the current copy's inst_src
+// (device-resident transforms; the caller passes the host's inst_xf otherwise).  The instance state is sized, the
+// current copy and icur are left alone: the caller puts a tree into the same copy and commits.
+int next_instance_records(prt_ctx* c, const float* xf_host, const float* xf_dev, size_t& nx_out) {
   const int32_t n = (int32_t)c->inst_mesh.size();
-  const bool use_tlas = c->use_tlas;
-  const bool on_dev = xf_dev || c->xf_device;
-  PRT_TRY(worker_ok(c));
   for (int32_t i = 0; i < n; i++)
     if (c->inst_mesh[i] >= c->mesh_host.size()) return fail(PRT_ERR_INVALID_ARGUMENT, "instance references a missing mesh");
-  PRT_TRY(size_instance_state(c, n, use_tlas));
-  if (use_tlas) PRT_TRY(tlas_topology(c, n));
+  PRT_TRY(size_instance_state(c, n, c->use_tlas));
   const size_t nx = (c->icur + 1) % c->isets.size();
   InstSet& cur = c->isets[c->icur];
   InstSet& X = c->isets[nx];
   for (size_t k = 0; k < X.nuse; k++) HIP_TRY(hipStreamWaitEvent(c->stream, X.uses[k].second, 0));
   X.nuse = 0;
-  if (!on_dev) {  // the records' input filled on the host, as ensure_instances fills it
+  if (xf_host) {  // the records' input filled on the host, as ensure_instances fills it
     c->inst_stage.resize(n);
-    fill_inst_src(c, c->inst_stage.data());
+    fill_inst_src(c, xf_host, c->inst_stage.data());
     PRT_TRY(stage_upload(c, X.inst_src.p, c->inst_stage.data(), sizeof(InstSrc) * (size_t)n));
     c->inst_tab_ok = false;  // (the table was not brought up to what this refill read)
   } else {
@@ -350,6 +350,28 @@ int refit_instances(prt_ctx* c, const float* xf_dev) {
     else return fail(PRT_ERR_HIP, "instance update: one copy of the instance state");  // (the ring holds at least two)
   }
   HIP_TRY(launch_refit(c->stream, X.inst_src.as<InstSrc>(), n, X.inst.as<InstDev>()));
+  nx_out = nx;
+  return PRT_OK;
+}
+
+// prt_update_instances and, while the transforms are device-resident, every refresh of the instance records: the
+// next copy of the instance state from new transforms (or from the same ones under new kinds or mesh boxes), with the
+// instance BVH refitted over it (prt_tlas_refit.h).  xf_dev: packed 4x4 matrices in device memory; null: the host's
+// inst_xf, or, while prt_ctx::xf_device, the transforms kept in the current copy's inst_src.  Everything is enqueued on
+// the context stream: no host build, no worker job, no wait for the GPU.
+int refit_instances(prt_ctx* c, const float* xf_dev) {
+  const int32_t n = (int32_t)c->inst_mesh.size();
+  const bool use_tlas = c->use_tlas;
+  const bool on_dev = xf_dev || c->xf_device;
+  PRT_TRY(worker_ok(c));
+  for (int32_t i = 0; i < n; i++)
+    if (c->inst_mesh[i] >= c->mesh_host.size()) return fail(PRT_ERR_INVALID_ARGUMENT, "instance references a missing mesh");
+  PRT_TRY(size_instance_state(c, n, use_tlas));
+  if (use_tlas) PRT_TRY(tlas_topology(c, n));
+  size_t nx = 0;
+  PRT_TRY(next_instance_records(c, on_dev ? nullptr : c->inst_xf.data(), xf_dev, nx));
+  InstSet& cur = c->isets[c->icur];
+  InstSet& X = c->isets[nx];
   if (use_tlas)  // deepest level first, the root last: every child's box is written before its parent reads it
     for (size_t lv = c->tlas_level_ends.size(); lv-- > 0;) {
       const uint32_t b = lv ? c->tlas_level_ends[lv - 1] : 0u;
@@ -392,7 +414,7 @@ int ensure_instances(prt_ctx* c) {
   // pinned memory cost ~10 ms per 10,000 instances on the GPU box, profiles/r06_tlas_drift.txt)
   std::vector<InstSrc>& src = c->inst_stage;
   src.resize(n);
-  fill_inst_src(c, src.data());
+  fill_inst_src(c, c->inst_xf.data(), src.data());
   // the copy of the instance state this update writes: the next one in the ring (frames in flight + 1 copies), once
   // the context stream has waited for the frames that read it.  Every copy and the scratch of prt_update_instances
   // are sized here, for n, so that later updates never reallocate
@@ -845,6 +867,97 @@ int prt_update_instances(prt_ctx* c, const float* xf, int32_t n, uint32_t in_fla
   c->shade_epoch++;
   c->inst_epoch++;  // transforms, boxes and the instance BVH changed: kept primary hits and light visibility are stale
   PRT_FOR_MEMBERS(prt_update_instances(m, xf, n, in_flags));
+  return PRT_OK;
+}
+
+int prt_rebuild_instances(prt_ctx* c, const float* xf, int32_t n, uint32_t in_flags, int32_t builder) {
+  if (!c) return fail(PRT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  if (builder == PRT_BUILDER_HOST_SAH || builder == PRT_BUILDER_HOST_SBVH)
+    return fail(PRT_ERR_UNSUPPORTED, "instance rebuild: the host builders rebuild through prt_set_instances only");
+  if (builder != PRT_BUILDER_GPU_LBVH && builder != PRT_BUILDER_GPU_PLOC)
+    return fail(PRT_ERR_INVALID_ARGUMENT, "bad instance BVH builder");
+  if (in_flags & ~PRT_IN_DEVICE) return fail(PRT_ERR_INVALID_ARGUMENT, "unknown input flags");
+  if (!xf && in_flags) return fail(PRT_ERR_INVALID_ARGUMENT, "instance rebuild without transforms takes no input flags");
+  if (c->mesh_host.empty()) return fail(PRT_ERR_NOT_READY, "no meshes: call prt_set_meshes");
+  if (c->inst_mesh.empty()) return fail(PRT_ERR_NOT_READY, "no instances: call prt_set_instances");
+  if (n != (int32_t)c->inst_mesh.size())
+    return fail(PRT_ERR_INVALID_ARGUMENT, "instance rebuild: the instance count must stay (a new set needs prt_set_instances)");
+  const bool dev_in = xf && (in_flags & PRT_IN_DEVICE) != 0;
+  if (dev_in && c->sh_kind == 2) return fail(PRT_ERR_UNSUPPORTED, "device transforms on a local shard group");
+  if (dev_in && (reinterpret_cast<uintptr_t>(xf) & 15u))
+    return fail(PRT_ERR_INVALID_ARGUMENT, "device transforms must be 16-byte aligned");
+  PRT_TRY(worker_ok(c));
+  // (no join of the frames in flight: the rebuild writes the next copy of the instance state, InstSet)
+  HIP_TRY(hipSetDevice(c->device));
+  if (c->iset_n != n) {  // the set was never brought to the device (prt_set_instances came before the meshes): its
+    c->inst_dirty = true;  // first build, from the host's transforms, decides between the list and the tree
+    c->tlas_dirty = true;
+    PRT_TRY(ensure_instances(c));
+  }
+  if (!c->use_tlas) {  // the linear list has no tree: the call is prt_update_instances (every member included)
+    if (!xf) return PRT_OK;
+    return prt_update_instances(c, xf, n, in_flags);
+  }
+  const size_t N = (size_t)n;
+  if (c->tb_fat.bytes < 48 * N || c->tb_nodes.bytes < sizeof(Node8) * N || c->tb_tris.bytes < sizeof(TriMT) * N) {
+    PRT_TRY(wait_stream(c, "prt_rebuild_instances"));  // (an earlier rebuild's kernels read the scratch this frees)
+    HIP_TRY(c->tb_fat.ensure(48 * N));
+    HIP_TRY(c->tb_nodes.ensure(sizeof(Node8) * N));
+    HIP_TRY(c->tb_tris.ensure(sizeof(TriMT) * N));
+  }
+  // The next copy's records, then the builder's input from their boxes.  Nothing the frames read changes before the
+  // commit below: a failure from here on leaves a half-written copy that is not the current one.
+  size_t nx = 0;
+  PRT_TRY(next_instance_records(c, dev_in ? nullptr : xf ? xf : c->xf_device ? nullptr : c->inst_xf.data(),
+                                dev_in ? xf : nullptr, nx));
+  InstSet& X = c->isets[nx];
+  HIP_TRY(launch_tlas_prims(c->stream, X.inst.as<InstDev>(), n, c->tb_fat.as<float4>()));
+  // The build, into the context's scratch.  The builder synchronises the context stream once per PLOC iteration and
+  // once per tree level; the wait before it is the bounded one of an RCCL context.
+  PRT_TRY(wait_stream(c, "prt_rebuild_instances"));
+  GpuBlasInfo gi = {};
+  std::vector<uint32_t> ends;
+  const hipError_t be = gpu_build_blas8(c->stream, c->tb_fat.as<float>(), n, /*max_leaf*/ 1, c->tb_nodes.as<Node8>(),
+                                        c->tb_tris.as<TriMT>(), &gi, builder == PRT_BUILDER_GPU_PLOC, &ends);
+  if (be != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(PRT_ERR_HIP, std::string("instance rebuild: the device build failed: ") + hipGetErrorString(be));
+  }
+  bool ok = gi.nodes >= 1 && gi.nodes <= (uint32_t)n && gi.tris == (uint32_t)n && gi.depth >= 1 &&
+            ends.size() == (size_t)gi.depth && ends.back() == gi.nodes;
+  for (size_t d = 1; ok && d < ends.size(); d++) ok = ends[d] > ends[d - 1];
+  if (!ok) return fail(PRT_ERR_HIP, "instance rebuild: the device build returned no usable tree");
+  if (const char* tr = std::getenv("PRT_REBUILD_TRACE"); tr && std::atoi(tr) == 1)  // (scripts/instance_rebuild_time.py)
+    std::fprintf(stderr, "prt_rebuild_instances: %d instances, %s: %u nodes, %d levels, the builder waited for the stream %u times\n",
+                 n, builder == PRT_BUILDER_GPU_PLOC ? "GPU_PLOC" : "GPU_LBVH", gi.nodes, gi.depth, gi.syncs);
+  if (c->max_depth + gi.depth > kMaxBvhDepth)
+    return fail(PRT_ERR_UNSUPPORTED, "instance rebuild: the new instance BVH is deeper than the traversal stacks cover");
+  // The commit, in the context stream's order: the tree as an instance BVH into the next copy, the level order of a
+  // later refit (the builder emits level d as [ends[d - 1], ends[d]): the identity), then the host's view of it
+  // (the builder is through with its input: the fat triangles' 48 bytes per instance are the 12 per node of the order)
+  HIP_TRY(launch_tlas_finish(c->stream, c->tb_nodes.as<Node8>(), c->tb_tris.as<TriMT>(), gi.tris, gi.nodes, (uint32_t)n,
+                             ends.data(), ends.size(), c->tb_fat.as<uint32_t>(), X.tlas8.as<Node8>(),
+                             X.tlas_slot.as<uint32_t>()));
+  std::vector<uint32_t> order(gi.nodes);
+  for (uint32_t j = 0; j < gi.nodes; j++) order[j] = j;
+  PRT_TRY(stage_upload(c, c->tlas_order.p, order.data(), 4 * (size_t)gi.nodes));
+  c->tlas_nodes = gi.nodes;
+  c->tlas_level_ends = std::move(ends);
+  c->tlas_topo = true;  // (prt_read_tlas / prt_tlas_cost and the next refit never ask the worker for its stale tree)
+  // a deeper tree than the stacks were sized for: they are sized from stack_depth(c) at every launch
+  if (gi.depth > c->tlas_depth) c->tlas_depth = gi.depth;
+  c->icur = nx;
+  c->iset_n = n;
+  c->inst_dirty = false;
+  c->tlas_dirty = false;
+  if (xf && !dev_in) {
+    c->inst_xf.assign(xf, xf + 16 * N);
+    c->xf_device = false;
+  }
+  if (dev_in) c->xf_device = true;
+  c->shade_epoch++;
+  c->inst_epoch++;  // transforms, boxes and the instance BVH changed: kept primary hits and light visibility are stale
+  PRT_FOR_MEMBERS(prt_rebuild_instances(m, xf, n, in_flags, builder));
   return PRT_OK;
 }
 

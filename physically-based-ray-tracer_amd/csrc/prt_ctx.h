@@ -272,6 +272,11 @@ struct prt_ctx {
   std::vector<uint32_t> tlas_level_ends;
   DevBuf tlas_order, tlas_box, inst_tab;
   bool inst_tab_ok = false;
+  // prt_rebuild_instances (prt_tlas_build.h): where the device builder reads the instances' fat triangles (48 bytes
+  // per instance) and leaves the new tree (80 bytes of nodes, 48 of records per instance) before it is committed to the
+  // next copy of the ring; sized by the first rebuild of an instance count and kept.  Once the builder is through
+  // with its input, tb_fat holds the canonical level order of the commit (12 bytes per node)
+  DevBuf tb_fat, tb_nodes, tb_tris;
   // sky, lights, camera
   DevBuf sky;
   int32_t skyw = 0, skyh = 0;

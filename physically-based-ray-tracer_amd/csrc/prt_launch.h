@@ -150,6 +150,17 @@ hipError_t launch_refit(hipStream_t s, const InstSrc* src, int32_t n, InstDev* o
 // the stream waits until *flag (coherent pinned host memory, device address) is nonzero; after `seconds` it stops
 // waiting and sets *err (prt_render.hip k_wait_host)
 hipError_t launch_wait_host(hipStream_t s, uint32_t* flag, uint32_t* err, double seconds);
+// prt_rebuild_instances (prt_tlas_build.hip; the definitions: prt_tlas_build.h).  launch_tlas_prims: the device
+// builder's input, three float4 per instance, from the boxes of the records inst[0 .. n).  launch_tlas_finish: the
+// builder's tree nodes[0 .. n_nodes) over the records tris[0 .. n_tris), whose level d is [level_ends[d - 1],
+// level_ends[d]) (host array), as an instance BVH into dst / dst_slot (80 and 32 bytes per node; neither may overlap
+// nodes), each level in its canonical order: the same tree gives the same bytes wherever the builder's atomic counters
+// placed its nodes.  The levels stay where they are.  order_scratch: 12 bytes per node
+struct TriMT;
+hipError_t launch_tlas_prims(hipStream_t s, const InstDev* inst, int32_t n, float4* fat);
+hipError_t launch_tlas_finish(hipStream_t s, const Node8* nodes, const TriMT* tris, uint32_t n_tris, uint32_t n_nodes,
+                              uint32_t ninst, const uint32_t* level_ends, size_t levels, uint32_t* order_scratch,
+                              Node8* dst, uint32_t* dst_slot);
 hipError_t launch_primary_hits(const LaunchCfg& c, const SceneDev& S, const TileMap& M, HitOut* out, Counters* cnt);
 hipError_t launch_intersect(const LaunchCfg& c, const SceneDev& S, int32_t n, const float* O, const float* D,
                             const float* tmax, HitOut* out);

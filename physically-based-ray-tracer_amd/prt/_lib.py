@@ -41,7 +41,7 @@ EXPORTS = [
     "prt_snapshot_mesh", "prt_render_aov_deform", "prt_reproject_deform",
     "prt_set_mesh_skin", "prt_skin_mesh",
     "prt_blas_cost", "prt_rebuild_mesh",
-    "prt_update_instances", "prt_tlas_cost", "prt_read_tlas",
+    "prt_update_instances", "prt_rebuild_instances", "prt_tlas_cost", "prt_read_tlas",
 ]
 SHARD_ID_BYTES = 128
 SHARD_NONE, SHARD_RCCL, SHARD_GROUP = 0, 1, 2  # prt_shard_info.transport
@@ -191,6 +191,7 @@ def load():
         "prt_read_blas_tris": ([vp, i32, vp, C.c_uint64, C.POINTER(C.c_uint64)], C.c_int),
         "prt_set_instances": ([vp, vp, vp, i32], C.c_int),
         "prt_update_instances": ([vp, vp, i32, u32], C.c_int),
+        "prt_rebuild_instances": ([vp, vp, i32, u32, i32], C.c_int),
         "prt_tlas_cost": ([vp, C.POINTER(C.c_double)], C.c_int),
         "prt_read_tlas": ([vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int),
         "prt_set_lights": ([vp, C.POINTER(Lights)], C.c_int),

@@ -319,6 +319,7 @@ class Context:
         xf = _f32(np.stack([T for _, T in scene.blases]).reshape(-1))
         mi = np.ascontiguousarray([m for m, _ in scene.blases], np.uint32)
         check(L.prt_set_instances(self.h, xf.ctypes.data, mi.ctypes.data, len(scene.blases)))
+        self._ninst = len(scene.blases)
         self.set_materials(scene.materials)
         self.set_area_light(scene.areaLights[0] if scene.areaLights else None)
         lt = _lib.Lights()
@@ -358,6 +359,7 @@ class Context:
         xf = _f32(np.stack([T for _, T in blases]).reshape(-1))
         mi = np.ascontiguousarray([m for m, _ in blases], np.uint32)
         check(self.L.prt_set_instances(self.h, xf.ctypes.data, mi.ctypes.data, len(blases)))
+        self._ninst = len(blases)
 
     def update_instances(self, transforms, device=False):
         """prt_update_instances: the instances of the last set_instances / set_scene take new transforms; mesh indices
@@ -382,6 +384,31 @@ class Context:
         if xf.size % 16:
             raise ValueError("update_instances: 16 floats per instance")
         check(self.L.prt_update_instances(self.h, xf.ctypes.data, xf.size // 16, 0))
+
+    def rebuild_instances(self, transforms=None, builder=_lib.BUILDER_GPU_PLOC, device=False):
+        """prt_rebuild_instances: update_instances with a fresh device build of the instance BVH in place of the refit
+        (builder: _lib.BUILDER_GPU_LBVH or BUILDER_GPU_PLOC).  `transforms` as update_instances takes them -- a float32
+        array, or a torch tensor on this context's device (taken as device memory, with or without device=True), or
+        (pointer, n) with device=True; None: the instances stay where they are and only the tree is rebuilt, from the
+        transforms the context holds (on the device, after a device update).  Blocks until the builder is through."""
+        if transforms is None:
+            check(self.L.prt_rebuild_instances(self.h, None, getattr(self, "_ninst", 0), 0, int(builder)))
+            return
+        if device or hasattr(transforms, "data_ptr"):
+            if hasattr(transforms, "data_ptr"):
+                if not transforms.is_cuda or not transforms.is_contiguous() or str(transforms.dtype) != "torch.float32" \
+                        or transforms.numel() % 16:
+                    raise ValueError("rebuild_instances: transforms must be a contiguous torch.float32 tensor of 16 per "
+                                     "instance on the device")
+                ptr, n = transforms.data_ptr(), transforms.numel() // 16
+            else:
+                ptr, n = transforms
+            check(self.L.prt_rebuild_instances(self.h, int(ptr), int(n), _lib.IN_DEVICE, int(builder)))
+            return
+        xf = _f32(transforms).reshape(-1)
+        if xf.size % 16:
+            raise ValueError("rebuild_instances: 16 floats per instance")
+        check(self.L.prt_rebuild_instances(self.h, xf.ctypes.data, xf.size // 16, 0, int(builder)))
 
     def tlas_cost(self):
         """prt_tlas_cost: the SAH cost of the instance BVH as it stands on the device (prt_blas_cost's measure, a leaf
@@ -1081,6 +1108,18 @@ class Renderer:
     def TlasCost(self):
         """The SAH cost of the instance BVH as it stands (prt_tlas_cost)."""
         return self.ctx.tlas_cost()
+
+    def RebuildInstances(self, transforms=None, builder=_lib.BUILDER_GPU_PLOC, device=False):
+        """UpdateInstances with a fresh device build of the instance BVH in place of the refit (prt_rebuild_instances);
+        transforms=None rebuilds over the instances where they are, device-resident transforms included.  TlasCost()
+        tells when it pays: the library has no policy."""
+        if transforms is not None and not device and not hasattr(transforms, "data_ptr"):
+            T = _f32(transforms).reshape(-1, 4, 4)
+            if len(T) != len(self.scene.blases):
+                raise ValueError("RebuildInstances: one transform per instance")
+            self.scene.blases = [(m, T[i].copy()) for i, (m, _) in enumerate(self.scene.blases)]
+        self.ctx.rebuild_instances(transforms, builder=builder, device=device)
+        self.ctx.reset_accumulation(full=True)
 
     def RebuildModel(self, index, mesh=None, builder=_lib.BUILDER_GPU_PLOC):
         """UpdateModel with a fresh device build of the model's BLAS in place of the refit (prt_rebuild_mesh); mesh=None
