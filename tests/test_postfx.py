@@ -2,7 +2,9 @@
 screen pass of Renderer::Tick (Core/Renderer.cpp:107-133).  The reference cannot run here (Windows/SDL
 app), so the restatement is pinned by the properties its code implies: distortion 0 is a rectilinear
 projection, a zero vignette exponent and unit grading leave the pixel alone, the aberration blends the
-accumulators of the neighbours in the row-walk order.  Parity unpinned against reference binaries."""
+accumulators of the neighbours in the row-walk order.  The screen pass at sample counts that differ along a row,
+the fold that feeds it and the AA jitter are held to a literal reference in tests/fold_ref.py (tests/test_fold_ref.py
+on the oracle, tests/test_gpu_fold.py on the device)."""
 import numpy as np
 import pytest
 
