@@ -76,8 +76,17 @@ typedef struct {
 } prt_texture;
 
 /* one Model (Core/Model.h:36-44).  T = tri_count, V = vertex_count.
- * fixed_uvs must be >= 0: values >= 1 wrap around the texture, and a negative UV indexes outside the texture as
- * in the reference (Core/Scene.cpp:82-83,163-164) and is undefined. */
+ * fixed_uvs may hold any float, also where the host never sees them (PRT_IN_DEVICE).  Texel addressing is one total
+ * function of the interpolated uv, per component, with n the ALBEDO map's width or height and x = uv * (float)n
+ * (one float multiply):
+ *     !(fabsf(x) < 2147483648.0f)  ->  0                       NaN, +-inf, |x| >= 2^31
+ *     otherwise  r = (int)x % n;  if (r < 0) r += n;  ->  r    truncation toward zero, then a wrap into [0, n)
+ * and every map is read at texel column + row * w, always inside [0, w * h).  For x > -1 this is the reference's
+ * (int)x % n (Core/Scene.cpp:82-83,163-164) bit for bit: values >= 1 repeat the texture.  The reference itself
+ * indexes outside the texture for x <= -1 and is undefined where the cast is; here a negative uv repeats the
+ * texture as well.  Truncation, not floor: -1 < x < 0 addresses texel 0, as it does in the reference (the tiny
+ * negative uv that w = 1 - u - v rounding can give on a triangle's edge), so texel 0 is two texels wide around
+ * uv = 0 and the tiling is not translation-invariant across 0: texel k < 0 covers (k - 1, k], not [k, k + 1). */
 typedef struct {
     int32_t tri_count;
     int32_t vertex_count;
@@ -842,6 +851,10 @@ int prt_reproject_deform(prt_ctx* ctx, const prt_temporal_params* params, int32_
  *   FRESNEL      evalFresnel Schlick (:84-87)          in f0[0..2] f90[3] NdotS[4]                out F[0..2]
  *   SHADOWED_F90 shadowedF90 (:100-104)                in F0[0..2]                                out f90[0]
  *   VNDF         sampleGGXVNDF (:224-269)              in Ve[0..2] alphaX[3] alphaY[4] u[5..6]    out H[0..2]
+ *   TEXEL        the texel addressing of prt_mesh.fixed_uvs (Core/Scene.cpp:79-85,160-165) with a w x h albedo
+ *                                                      in uv[0..1] w[2] h[3]                      out iu[0] iv[1]
+ *                w and h are integers in 1..16384 held in floats, anything else is PRT_ERR_INVALID_ARGUMENT; iu and
+ *                iv are the texel's column and row (index = iu + iv * w) as floats.
  * material = base rgb, metalness, emissive rgb, roughness (MaterialProperties, Core/BRDF.h:165-176). */
 #define PRT_PROBE_EVAL 0
 #define PRT_PROBE_PROBABILITY 1
@@ -851,6 +864,7 @@ int prt_reproject_deform(prt_ctx* ctx, const prt_temporal_params* params, int32_
 #define PRT_PROBE_FRESNEL 5
 #define PRT_PROBE_SHADOWED_F90 6
 #define PRT_PROBE_VNDF 7
+#define PRT_PROBE_TEXEL 8
 int prt_brdf_probe(prt_ctx* ctx, int32_t op, int32_t n, const float* in, float* out);
 
 /* ---- BLAS builder (the reference builds on the CPU, Core/tiny_bvh.h:1968-2284,3706-3781)

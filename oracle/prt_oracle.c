@@ -726,9 +726,16 @@ static inline f2 hit_uv(const mesh_t* M, uint32_t prim, float u, float v, float 
     r.y = v * t[5] + u * t[3] + w * t[1];
     return r;
 }
+/* (int)x % n of :160-165 made total (include/prt.h, prt_mesh.fixed_uvs): truncation toward zero, then a wrap into
+ * [0, n); 0 where the cast is undefined (NaN, +-inf, |x| >= 2^31).  Unchanged for every x > -1. */
+static inline int texel_coord(float x, int n) {
+    if (!(fabsf(x) < 2147483648.0f)) return 0;
+    int r = (int)x % n;
+    return r < 0 ? r + n : r;
+}
 static inline int texel_index(const tex_t* A, f2 uv) {                     /* :160-165 */
-    int iu = (int)(uv.x * (float)A->w) % A->w;
-    int iv = (int)(uv.y * (float)A->h) % A->h;
+    int iu = texel_coord(uv.x * (float)A->w, A->w);
+    int iv = texel_coord(uv.y * (float)A->h, A->h);
     return iu + iv * A->w;
 }
 static inline f3 geometry_normal(const orc_scene* s, uint32_t inst, uint32_t prim) {   /* :47-58 */
@@ -1350,6 +1357,15 @@ int orc_brdf_probe(int32_t op, int32_t n, const float* in, float* out) {
             f2 u = {a[5], a[6]};
             f3 H = sample_vndf(v3(a[0], a[1], a[2]), a[3], a[4], u);
             o[0] = H.x; o[1] = H.y; o[2] = H.z;
+            break;
+        }
+        case 8: { /* PRT_PROBE_TEXEL: texel_index with a w x h albedo, as column and row */
+            if (!(a[2] >= 1.0f && a[2] <= 16384.0f && a[3] >= 1.0f && a[3] <= 16384.0f) ||
+                a[2] != (float)(int)a[2] || a[3] != (float)(int)a[3]) return -1;
+            tex_t A = {(int32_t)a[2], (int32_t)a[3], NULL};
+            f2 uv = {a[0], a[1]};
+            int px = texel_index(&A, uv);
+            o[0] = (float)(px % A.w); o[1] = (float)(px / A.w);
             break;
         }
         default: return -1;

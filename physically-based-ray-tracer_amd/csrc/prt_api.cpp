@@ -1275,9 +1275,16 @@ int prt_render_aov_deform(prt_ctx* c, int32_t W, int32_t H, uint32_t flags, floa
 }
 
 int prt_brdf_probe(prt_ctx* c, int32_t op, int32_t n, const float* in, float* out) {
-  if (!c || n < 0 || (n > 0 && (!in || !out)) || op < PRT_PROBE_EVAL || op > PRT_PROBE_VNDF)
+  if (!c || n < 0 || (n > 0 && (!in || !out)) || op < PRT_PROBE_EVAL || op > PRT_PROBE_TEXEL)
     return fail(PRT_ERR_INVALID_ARGUMENT, "bad BRDF probe arguments");
   if (n == 0) return PRT_OK;
+  if (op == PRT_PROBE_TEXEL)
+    for (int32_t i = 0; i < n; i++)
+      for (int k = 2; k < 4; k++) {
+        const float d = in[24 * (size_t)i + k];  // the kernel divides by it
+        if (!(d >= 1.0f && d <= 16384.0f) || d != (float)(int32_t)d)
+          return fail(PRT_ERR_INVALID_ARGUMENT, "texel probe: w and h must be integers in 1..16384");
+      }
   PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
   HIP_TRY(hipSetDevice(c->device));
   DevBuf din, dout;

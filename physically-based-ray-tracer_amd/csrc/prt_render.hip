@@ -310,6 +310,13 @@ __global__ void __launch_bounds__(kBlock) k_brdf_probe(int32_t op, int32_t n, co
       o[0] = H.x; o[1] = H.y; o[2] = H.z;
       break;
     }
+    case 8: {  // PRT_PROBE_TEXEL: w and h were checked on the host (prt_brdf_probe)
+      TexDev A;
+      A.offset = 0; A.w = (int32_t)a[2]; A.h = (int32_t)a[3]; A.pad = 0;
+      const uint32_t px = texel_index(A, make_float2(a[0], a[1]));
+      o[0] = (float)(px % (uint32_t)A.w); o[1] = (float)(px / (uint32_t)A.w);
+      break;
+    }
     default:
       break;
   }

@@ -159,10 +159,18 @@ struct HitAttr {
   uint32_t kind;  // instance material kind (kMatDielectric takes Trace's dielectric branch)
 };
 
-// uv = v*uv2 + u*uv1 + w*uv0 (Scene.cpp:75-77,156-158); texel index with ALBEDO dims (:79-85,160-165)
+// uv = v*uv2 + u*uv1 + w*uv0 (Scene.cpp:75-77,156-158); texel index with ALBEDO dims (:79-85,160-165).
+// texel_coord is total (include/prt.h, prt_mesh.fixed_uvs): x = uv * n truncates toward zero and wraps into [0, n),
+// the reference's (int)x % n wherever that is defined and >= 0 (every x > -1); NaN, +-inf and |x| >= 2^31, where the
+// cast is undefined, give 0.  So texel_index is always in [0, w * h), and it is the only index S.texels is read at.
+__device__ __forceinline__ int texel_coord(float x, int n) {
+  if (!(fabsf(x) < 2147483648.0f)) return 0;
+  const int r = (int)x % n;
+  return r < 0 ? r + n : r;
+}
 __device__ __forceinline__ uint32_t texel_index(const TexDev& A, float2 uv) {
-  const int iu = (int)(uv.x * (float)A.w) % A.w;
-  const int iv = (int)(uv.y * (float)A.h) % A.h;
+  const int iu = texel_coord(uv.x * (float)A.w, A.w);
+  const int iv = texel_coord(uv.y * (float)A.h, A.h);
   return (uint32_t)(iu + iv * A.w);
 }
 

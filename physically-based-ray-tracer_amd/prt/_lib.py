@@ -18,6 +18,9 @@ IN_DEVICE = 1  # prt_update_mesh / prt_skin_mesh / prt_update_instances: the arr
 OUT_TIMED = 2  # prt_render_aov / prt_denoise: record the per-pass HIP events prt_denoise_timings reads
 DENOISE_TIMINGS = 10
 BUILDER_HOST_SAH, BUILDER_GPU_LBVH, BUILDER_HOST_SBVH, BUILDER_GPU_PLOC = 0, 1, 2, 3
+# prt_brdf_probe ops (PRT_PROBE_*)
+(PROBE_EVAL, PROBE_PROBABILITY, PROBE_INDIRECT, PROBE_GGX_D, PROBE_SMITH_G2, PROBE_FRESNEL, PROBE_SHADOWED_F90,
+ PROBE_VNDF, PROBE_TEXEL) = range(9)
 
 # Renderer::RENDER_STATES (Core/Renderer.h:37-46)
 MODE_BRDF, MODE_BASECOLOR, MODE_GEOMETRYNORMAL, MODE_SHADINGNORMAL, MODE_METAL, MODE_ROUGHNESS, MODE_EMISSIVE = range(7)

@@ -160,12 +160,42 @@ def sample_sky(sky, D):
 
 
 # ------------------------------------------------------------------------------------------------ texels
-def texel_index(uv, albedo_w, albedo_h):
-    """Scene.cpp:79-85,160-165: (int)(uv.x * w) % w + ((int)(uv.y * h) % h) * w with the ALBEDO texture's w and h,
-    whichever map is then read.  C semantics: the cast truncates and % keeps the dividend's sign (uv >= 0 here)."""
+# planted defects of texel_index (slip=), to show that a comparison against it can see a wrong rule
+TEXEL_SLIPS = ("floor", "abs", "clamp", "no_negative_wrap", "wrap_v_with_w", "no_range_guard")
+_INT_MIN, _INT_MAX = -(1 << 31), (1 << 31) - 1
+
+
+def _texel_coord(c, n, slip, wrap_n=None):
+    """One component of texel_index: the float32 array c times the size n, as an int64 array."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        x = np.asarray(c, F) * F(n)                              # one float32 multiply
+        inside = np.abs(x) < F(2147483648.0)                     # False for NaN, +-inf, |x| >= 2^31
+    whole = np.trunc(np.where(inside, x, F(0))).astype(np.int64)    # truncation toward zero
+    if slip == "floor":
+        whole = np.floor(np.where(inside, x, F(0))).astype(np.int64)
+    if slip == "abs":
+        whole = np.abs(whole)
+    if slip == "no_range_guard":   # the cast as the device's conversion does it: NaN -> 0, the rest saturates
+        sat = np.where(np.isnan(x), F(0), np.clip(x.astype(np.float64), _INT_MIN, _INT_MAX))
+        whole = np.trunc(sat).astype(np.int64)
+    if slip == "clamp":
+        return np.clip(whole, 0, n - 1)
+    if slip == "no_negative_wrap":   # C's %, which keeps the dividend's sign
+        return np.fmod(whole, np.int64(n))
+    return np.mod(whole, np.int64(n if wrap_n is None else wrap_n))   # numpy's mod of integers lies in [0, n)
+
+
+def texel_index(uv, albedo_w, albedo_h, slip=None):
+    """The texel every map of a mesh is read at, for any float32 uv: column + row * w with the ALBEDO texture's w and
+    h, whichever map is then read (Scene.cpp:79-85,160-165).  Per component, with x = uv * n in float32: x is
+    truncated toward zero and wrapped into [0, n); where x is NaN, infinite or |x| >= 2^31 the component is 0.  For
+    x > -1 that is the reference's (int)x % n; the reference indexes outside the texture below that and is undefined
+    where the cast is, and include/prt.h (prt_mesh.fixed_uvs) defines the rest as stated here.  int64 throughout, so
+    nothing overflows.  slip: None, or one of TEXEL_SLIPS."""
+    assert slip is None or slip in TEXEL_SLIPS
     uv = np.asarray(uv, F)
-    iu = np.fmod(np.trunc(uv[..., 0] * F(albedo_w)).astype(np.int64), albedo_w)
-    iv = np.fmod(np.trunc(uv[..., 1] * F(albedo_h)).astype(np.int64), albedo_h)
+    iu = _texel_coord(uv[..., 0], albedo_w, slip)
+    iv = _texel_coord(uv[..., 1], albedo_h, slip, albedo_w if slip == "wrap_v_with_w" else None)
     return iu + iv * albedo_w
 
 

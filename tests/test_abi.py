@@ -23,6 +23,14 @@ def test_header_symbols_exported():
     assert L.prt_abi_version() == _lib.ABI_VERSION == 10
 
 
+def test_probe_ops_match_header():
+    """Every PRT_PROBE_* of include/prt.h has the same value in prt/_lib.py, PRT_PROBE_TEXEL = 8 among them."""
+    hdr = open(os.path.join(ROOT, "include", "prt.h")).read()
+    ops = {name: int(val) for name, val in re.findall(r"^#define PRT_PROBE_(\w+) (\d+)$", hdr, re.M)}
+    assert len(ops) == 9 and ops["TEXEL"] == 8
+    assert ops == {name: getattr(_lib, "PROBE_" + name) for name in ops}
+
+
 def test_ingest_header_symbols_exported():
     """include/prt_ingest.h (host-side ingest helpers) against libprt_ingest.so."""
     hdr = open(os.path.join(ROOT, "include", "prt_ingest.h")).read()

@@ -6,8 +6,9 @@ the expected values come from scene_ref, written from the reference's source lin
 docstring): bit identity for the float32 restatements, rtol = atol = scene_ref.CLOSED_TOL for the float64 closed
 forms.  tests/test_scene_ref.py runs the same checks (the check_* functions below) against the oracle on the CPU.
 
-The scenes are built here.  Every vertex UV is >= 0: a negative UV indexes outside the texel array, in the
-reference and here alike, and no test feeds one to the device.
+The scenes are built here.  In `attr`, `sky` and `lit` every vertex UV is >= 0, where texel addressing is the
+reference's own.  Negative, huge and boundary UVs, which include/prt.h (prt_mesh.fixed_uvs) defines beyond the
+reference, are `uv_scene`'s; tests/test_gpu_texel.py feeds them to the device and tests/test_texel_ref.py to the oracle.
 """
 import functools
 import types
@@ -101,6 +102,75 @@ def attr_scene():
             (0, _trs((-2.2, 0.2, 0.3), 0.6, 0.3, (1.6, 0.5, 0.8)))]
     return scenes.SceneData([m0, m1], tex, inst, _no_lights(), None, np.array([0.1, 3.2, -4.2], F),
                             np.array([0.0, 0.0, 0.0], F), "attr")
+
+
+# The constant UVs of `uv_scene`, by class (include/prt.h prt_mesh.fixed_uvs: any float is defined).  "boundary":
+# multiples of 1/8 or 1/4, texel boundaries of an 8x4 albedo, where the interpolation's rounding decides the side;
+# "huge": finite values whose product with the size passes 2^24 (the texel is the rounding's), reaches 2^31 exactly
+# (2^28 * 8), exceeds it, or overflows to infinity (3.4e38 * 8).
+UV_CLASSES = (
+    ("negative", (-0.3, -0.55, -1.7, -2.25, -0.05, -3.9, -0.999, -1.001, -7.4, -0.51, -1e-8, -0.125001)),
+    ("minus_one", (-1.0, -1.0)),
+    ("ge_2", (2.0, 2.6, 3.125, 17.3, 2.0000002, 255.9)),
+    ("boundary", (0.125, 0.25, 0.5, 0.75, -0.125, -0.25, 1.0, -2.0, 0.375, -0.5, -0.75, 1.5, 0.0, -0.0, -1.25, 2.25)),
+    ("huge", (1e9, 2.6e8, -2.6e8, -3e9, 3.4e38, -3.4e38, 16777216.0, -16777216.0, 268435456.0, -268435456.0, 5.3e8,
+              1e20)),
+)
+UV_VARYING = 12   # further triangles of `uv_scene` whose UVs vary across the triangle, class "straddle"
+
+
+def uv_triangle_classes():
+    """(class of u, class of v) of every triangle of `uv_scene`'s mesh; triangle i's constant UV is
+    (value[i], value[(7 i + 3) % n]) of UV_CLASSES flattened."""
+    flat = [(name, x) for name, xs in UV_CLASSES for x in xs]
+    n = len(flat)
+    const = [(flat[i], flat[(7 * i + 3) % n]) for i in range(n)]
+    return ([(a[0], b[0]) for a, b in const] + [("straddle", "straddle")] * UV_VARYING,
+            np.array([(a[1], b[1]) for a, b in const], F))
+
+
+@functools.lru_cache(None)
+def uv_scene(shift=0):
+    """Scene `uv`: one mesh of 60 small triangles in a 10 x 6 grid facing the camera, about 25 pixels each at 96x72,
+    under an 8x4 albedo, a 16x4 normal map, a 4x8 metalness map and an 8x4 emission map whose texels are distinct
+    within each map (in the metalness map the roughness and the metalness bytes are each distinct), so a wrong texel
+    shows in every mode.  48 triangles carry one UV at all three corners (UV_CLASSES); 12 carry UVs that vary across
+    the triangle around 0 and around -1 in each component, with a UV triangle of some area, so the normal-mapped
+    branch is finite there.  One identity instance, a directional and a point light on the camera's side.
+    shift != 0: the same scene with triangle i carrying triangle (i + shift)'s UVs."""
+    rng = np.random.default_rng(20240917)
+    classes, const = uv_triangle_classes()
+    T = len(classes)
+    assert T == 60 and const.shape == (48, 2)
+    tex = [rng.choice(1 << 24, 32, replace=False).astype(np.uint32).reshape(4, 8),
+           rng.choice(1 << 24, 64, replace=False).astype(np.uint32).reshape(4, 16),
+           ((rng.choice(256, 32, replace=False) << 8) | rng.choice(256, 32, replace=False)).astype(np.uint32).reshape(8, 4),
+           rng.choice(1 << 24, 32, replace=False).astype(np.uint32).reshape(4, 8)]
+    P = np.zeros((T, 3, 3))
+    for t in range(T):
+        x0, y0 = -3.0 + 0.6 * (t % 10), -1.8 + 0.6 * (t // 10)
+        P[t] = [[x0 + 0.04, y0 + 0.05, 0.0], [x0 + 0.56, y0 + 0.08, 0.0], [x0 + 0.27, y0 + 0.57, 0.0]]
+    P[:, :, 2] = rng.uniform(-0.1, 0.1, (T, 3))
+    N = np.array([0.0, 0.0, -1.0]) + rng.uniform(-0.4, 0.4, (T, 3, 3))
+    N *= rng.uniform(0.5, 2.0, (T, 3, 1)) / np.linalg.norm(N, axis=-1, keepdims=True)
+    UV = np.zeros((T, 3, 2), F)
+    UV[:48] = const[:, None, :]
+    for t in range(48, T):
+        centre = np.array([(0.0, -1.0)[(t >> 0) & 1], (0.0, -1.0)[(t >> 1) & 1]])
+        while True:
+            uv = centre + rng.uniform(-0.45, 0.45, (3, 2))
+            d1, d2 = uv[1] - uv[0], uv[2] - uv[0]
+            if abs(d1[0] * d2[1] - d1[1] * d2[0]) > 0.1 and (uv.min(0) < centre).all() and (uv.max(0) > centre).all():
+                break
+        UV[t] = uv
+    UV = np.roll(UV, -shift, 0)
+    mesh = _mesh(P, N, UV, albedo=0, normal=1, metalness=2, emission=3)
+    far, black = [0.0, 60.0, 0.0], [0.0, 0.0, 0.0]
+    lights = scenes.Lights(np.array([[0.5, 0.3, -2.0], far, far, far], F), np.array([[4.0, 3.0, 2.0], black, black, black], F),
+                           np.array([10.0, 20.0, -40.0], F), np.array([3.0, 2.5, 2.0], F),
+                           np.array([0.0, 3.0, 0.0], F), np.array(black, F), np.array([0.0, 1.0, 0.0], F))
+    return scenes.SceneData([mesh], tex, [(0, np.eye(4, dtype=F))], lights, None, np.array([0.0, 0.0, -5.0], F),
+                            np.array([0.0, 0.0, 0.0], F), "uv" if not shift else "uv-shift%d" % shift)
 
 
 @functools.lru_cache(None)

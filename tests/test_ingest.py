@@ -118,6 +118,34 @@ def test_gltf_model_arrays(tmp_path, glb):
     assert np.allclose(fn[0], [0, 0, 1]) and np.allclose(np.linalg.norm(fn, axis=1), 1, atol=1e-6)
 
 
+def test_gltf_tiled_texcoords_render_defined_texels(tmp_path, oracle_mod):
+    """A quad whose TEXCOORD_0 runs over [-1.5, 2.5]^2 -- a texture tiled four times, legal under glTF's default
+    REPEAT sampler -- loads with negative fixed_uvs (FlipUVs makes v = 1 - v, so already v > 1 goes negative), and
+    every pixel of its base-colour image from the oracle is the texel scene_ref.texel_index names."""
+    import scene_ref as R
+    P = np.array([[-1, -1, 0], [1, -1, 0], [-1, 1, 0], [1, 1, 0]], np.float32)
+    N = np.tile(np.array([0, 0, -1], np.float32), (4, 1))
+    UV = np.array([[-1.5, -1.5], [2.5, -1.5], [-1.5, 2.5], [2.5, 2.5]], np.float32)
+    m = ingest.load_model(_write_gltf(tmp_path, P, N, UV, np.array([0, 1, 2, 2, 1, 3])))
+    uv = m.fixed_uvs.reshape(-1, 2)
+    assert uv.min() == -1.5 and uv.max() == 2.5 and (uv[:, 1] < 0).any() and (uv[:, 0] < 0).any()
+    tex = np.random.default_rng(3).choice(1 << 24, 15, replace=False).astype(np.uint32).reshape(3, 5)
+    z = np.zeros(3, np.float32)
+    lights = scenes.Lights(np.zeros((4, 3), np.float32), np.zeros((4, 3), np.float32), z, z, z, z, np.array([0, 1, 0], np.float32))
+    sd = scenes.SceneData([m], [tex], [(0, np.eye(4, dtype=np.float32))], lights, None, np.array([0.1, 0.2, -3.0], np.float32),
+                          np.zeros(3, np.float32), "tiled quad")
+    W, H = 64, 48
+    osc = oracle_mod.OracleScene(sd, W, H)
+    t, u, v, prim, _ = osc.primary_hits(W, H)
+    hit = t < 1e30
+    assert hit.sum() > 500
+    got = osc.render(W, H, spp=1, bounces=1, flags=0, mode=1)[0][hit, :3]
+    want = R.material(m, sd.textures, prim[hit], u[hit], v[hit])
+    assert np.array_equal(got.view(np.uint32), want["base"].view(np.uint32))
+    huv = R.hit_uv(m, prim[hit], u[hit], v[hit])
+    assert (huv < -1).any() and (huv > 2).any() and np.unique(want["texel"]).size == tex.size
+
+
 def test_gltf_strip_and_generated_normals(tmp_path):
     P = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [1, 1, 0]], np.float32)
     m = ingest.load_model(_write_gltf(tmp_path, P, None, None, np.arange(4), mode=5))
