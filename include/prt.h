@@ -581,6 +581,39 @@ int prt_intersect(prt_ctx* ctx, int32_t n, const float* origins, const float* di
 int prt_occluded(prt_ctx* ctx, int32_t n, const float* origins, const float* dirs, const float* tmax,
                  int32_t* occluded);
 
+/* ---- ray queries on caller arrays, in stream order (ABI 10, additive; DESIGN.md "Ray queries") ----
+ * Both calls first join the frames in flight, run on the context stream (prt_set_stream) and mark their read of the
+ * instance state as a frame does: a later prt_update_instances, prt_rebuild_instances or prt_set_instances waits for
+ * them in stream order.  They touch neither the accumulation state nor the ray totals.  io_flags = 0: every pointer is
+ * host memory and the results are complete on return.  io_flags = PRT_OUT_DEVICE: every pointer is device memory on
+ * the context's device, 4-byte aligned, read and written only by the call's own kernels in the context stream's order;
+ * the call never waits on the host and, after the first call on a scene with at least this n, allocates nothing.  On a
+ * sharded or group context they run on the calling member over the whole scene.
+ * Errors: NULL context, n < 0, n > 1 << 28, missing arrays or unknown io_flags bits: PRT_ERR_INVALID_ARGUMENT; no
+ * scene: PRT_ERR_NOT_READY; n = 0: PRT_OK, nothing enqueued. */
+
+/* (ABI 10, additive) n rays on the persistent traversal kernels: origins / dirs float3 x n, tmax n floats or NULL
+ * (1e30 each).  hits[i]: the closest hit; occluded[i]: the any-hit answer; either may be NULL (both NULL:
+ * PRT_ERR_INVALID_ARGUMENT), both given are answered in one launch.  For a traversed ray hits[i] is bit for bit
+ * prt_intersect's record for that ray and tmax, occluded[i] prt_occluded's answer.
+ * A ray is never traversed when an origin or direction component is not finite, the direction has zero length (its
+ * float32 normalisation is not finite) or tmax is NaN or <= 0: it gets the miss record with t = tmax as given (or
+ * 1e30) and occluded = 0.  BVH deeper than 64 levels: PRT_ERR_UNSUPPORTED. */
+int prt_query_rays(prt_ctx* ctx, int32_t n, const float* origins, const float* dirs, const float* tmax,
+                   prt_hit* hits, int32_t* occluded, uint32_t io_flags);
+/* (ABI 10, additive) The shading inputs at n hit records, by the kernels' own hit-attribute code; traces nothing.
+ * Record i is a hit iff hits[i].t < (tmax ? tmax[i] : 1e30f): pass the tmax the query ran under (the miss record alone
+ * is ambiguous under a tmax).  A record that names no instance or primitive of the scene counts as a miss.  flags:
+ * only PRT_FLAG_NORMALMAP is read.  Every output may be NULL:
+ *   albedo_rgba     float4 x n: prt_render_aov's albedo_rgba; miss: 0,0,0,0
+ *   normal_depth    float4 x n: prt_render_aov's normal_depth (w = hits[i].t); miss: 0,0,0,1e30
+ *   geometry_normal float4 x n: xyz = the geometry normal as Trace uses it (Core/Scene.cpp:47-58), w = 1; miss: 0,0,0,0
+ *   material        float x 8n: MaterialProperties in prt_brdf_probe's order -- base rgb, metalness, emissive rgb,
+ *                   roughness; miss: eight zeros */
+int prt_query_surface(prt_ctx* ctx, int32_t n, const prt_hit* hits, const float* tmax, uint32_t flags,
+                      float* albedo_rgba, float* normal_depth, float* geometry_normal, float* material,
+                      uint32_t io_flags);
+
 /* ---- first-hit feature buffers and the denoiser they guide (ABI 10, additive; DESIGN.md "Denoiser") ----
  * Both calls first join the frames in flight and run on the context stream; with device pointers they do not wait
  * on the host.  Their scratch buffers belong to the context.  On a sharded or group context they run over the whole

@@ -350,6 +350,11 @@ struct prt_ctx {
   std::vector<const float*> snap_host;
   DevBuf snap_tab;
   DevBuf aov_off, rp_off;
+  // ray queries (prt_query_rays / prt_query_surface, prt_api_query.cpp): the staging of host rays (origins, directions,
+  // tmax) and of the hit / occlusion outputs, the fetch counters of k_query (kParts, cleared in stream order before each
+  // launch); the staging of host hit records and their tmax, and of the four surface outputs.  Allocated at first use
+  DevBuf q_in[3], q_hits, q_occ, q_ctr;
+  DevBuf qs_in[2], qs_out[4];
   // skinning (prt_set_mesh_skin / prt_skin_mesh, prt_skin.h): one binding per mesh (empty until the first binding
   // after a prt_set_meshes, which discards them all)
   std::vector<prt::host::SkinBinding> skin;

@@ -166,6 +166,27 @@ hipError_t launch_intersect(const LaunchCfg& c, const SceneDev& S, int32_t n, co
                             const float* tmax, HitOut* out);
 hipError_t launch_occluded(const LaunchCfg& c, const SceneDev& S, int32_t n, const float* O, const float* D,
                            const float* tmax, int32_t* out);
+// prt_query_rays (prt_query.hip k_query): n rays in the caller's arrays (device memory; tmax nullable = kFar each), the
+// closest hits into hits and / or the any-hit answers into occ (each nullable).  The live range of the persistent
+// launch is [0, total): nclosest closest-hit entries (n or 0), then the any-hit entries.  fctr: kParts fetch counters,
+// kCtrStride words apart, zero at launch
+struct QueryArgs {
+  const float* O;
+  const float* D;
+  const float* tmax;
+  HitOut* hits;
+  int32_t* occ;
+  uint32_t* fctr;
+  uint32_t nclosest, total;
+  int32_t coop_tail;  // cooperative traversal tail (prt_persist.h), the context's tunable as the render's
+};
+hipError_t launch_query(const LaunchCfg& c, const SceneDev& S, const QueryArgs& Q);
+// prt_query_surface (k_query_surface): the shading inputs at n hit records; a record is a hit when t < tmax (nullable =
+// kFar).  Every output nullable: albedo / normal_depth as launch_aov's, the geometry normal (w = 1), and the material as
+// two float4 per record (base rgb, metalness | emissive rgb, roughness); misses get the zeros include/prt.h defines
+hipError_t launch_query_surface(hipStream_t s, const SceneDev& S, int32_t n, bool normalmapped, const HitOut* hits,
+                                const float* tmax, float4* albedo, float4* normal_depth, float4* geo_normal,
+                                float4* material);
 // prt_brdf_probe: n records of 24 floats in, 8 out (include/prt.h PRT_PROBE_*)
 hipError_t launch_brdf_probe(hipStream_t s, int32_t op, int32_t n, const float* in, float* out);
 

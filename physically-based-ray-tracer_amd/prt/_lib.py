@@ -45,6 +45,7 @@ EXPORTS = [
     "prt_set_mesh_skin", "prt_skin_mesh",
     "prt_blas_cost", "prt_rebuild_mesh",
     "prt_update_instances", "prt_rebuild_instances", "prt_tlas_cost", "prt_read_tlas",
+    "prt_query_rays", "prt_query_surface",
 ]
 SHARD_ID_BYTES = 128
 SHARD_NONE, SHARD_RCCL, SHARD_GROUP = 0, 1, 2  # prt_shard_info.transport
@@ -220,6 +221,8 @@ def load():
         "prt_trace_primary": ([vp, i32, i32, vp, u32, C.POINTER(Stats)], C.c_int),
         "prt_intersect": ([vp, i32, vp, vp, vp, vp], C.c_int),
         "prt_occluded": ([vp, i32, vp, vp, vp, vp], C.c_int),
+        "prt_query_rays": ([vp, i32, vp, vp, vp, vp, vp, u32], C.c_int),
+        "prt_query_surface": ([vp, i32, vp, vp, u32, vp, vp, vp, vp, u32], C.c_int),
         "prt_brdf_probe": ([vp, i32, i32, vp, vp], C.c_int),
         "prt_get_scene_info": ([vp, C.POINTER(SceneInfo)], C.c_int),
         "prt_set_bvh_builder": ([vp, i32], C.c_int),

@@ -834,6 +834,86 @@ class Context:
         check(self.L.prt_occluded(self.h, O.shape[0], O.ctypes.data, D.ctypes.data, tm.ctypes.data, occ.ctypes.data))
         return occ
 
+    # -- ray queries on caller arrays, in stream order (include/prt.h prt_query_rays / prt_query_surface)
+    def _query_tensor(self, t, what, per, n=None):
+        """A contiguous float32 CUDA tensor of `per` floats per ray on this context's device (as update_instances
+        validates its transforms); returns its ray count."""
+        if str(t.dtype) != "torch.float32" or not t.is_cuda \
+                or not t.is_contiguous() or t.device.index != self.device or t.numel() % per \
+                or (n is not None and t.numel() != per * n):
+            raise ValueError(f"{what} must be a contiguous torch.float32 tensor of {per} per ray on cuda:{self.device}")
+        return t.numel() // per
+
+    def query_rays(self, origins, dirs, tmax=None, *, closest=True, any_hit=False):
+        """prt_query_rays: n arbitrary rays on the persistent traversal kernels; returns (hits, occluded), None for
+        the answer not asked for.  numpy arrays go through the host path and come back as numpy, complete on return
+        (hits in intersect()'s dtype).  Contiguous float32 CUDA tensors on this context's device are read in place in
+        the context stream's order, with no host wait: hits is an [n, 5] float32 tensor (t, u, v, then prim and inst,
+        which hits[:, 3:].view(torch.int32) reads), occluded an int32 tensor.  tmax None: 1e30 for every ray.  A ray
+        with a non-finite component, a zero direction or a tmax that is NaN or <= 0 is not traversed: a miss."""
+        if not closest and not any_hit:
+            raise ValueError("query_rays: closest or any_hit")
+        if hasattr(origins, "data_ptr"):
+            import torch
+            n = self._query_tensor(origins, "query_rays: origins", 3)
+            self._query_tensor(dirs, "query_rays: dirs", 3, n)
+            if tmax is not None:
+                self._query_tensor(tmax, "query_rays: tmax", 1, n)
+            hits = torch.empty((n, 5), dtype=torch.float32, device=origins.device) if closest else None
+            occ = torch.empty(n, dtype=torch.int32, device=origins.device) if any_hit else None
+            if n:  # (an empty tensor has no address to hand over, and an empty batch enqueues nothing)
+                check(self.L.prt_query_rays(self.h, n, origins.data_ptr(), dirs.data_ptr(),
+                                            tmax.data_ptr() if tmax is not None else None,
+                                            hits.data_ptr() if closest else None,
+                                            occ.data_ptr() if any_hit else None, _lib.OUT_DEVICE))
+            return hits, occ
+        O, D = _f32(origins).reshape(-1, 3), _f32(dirs).reshape(-1, 3)
+        n = O.shape[0]
+        if D.shape[0] != n:
+            raise ValueError("query_rays: one direction per origin")
+        tm = _f32(tmax).reshape(-1) if tmax is not None else None
+        if tm is not None and tm.size != n:
+            raise ValueError("query_rays: one tmax per ray")
+        hits = np.zeros(n, dtype=[("t", F32), ("u", F32), ("v", F32), ("prim", np.uint32),
+                                  ("inst", np.uint32)]) if closest else None
+        occ = np.zeros(n, np.int32) if any_hit else None
+        check(self.L.prt_query_rays(self.h, n, O.ctypes.data, D.ctypes.data, _ptr(tm), _ptr(hits), _ptr(occ), 0))
+        return hits, occ
+
+    def query_surface(self, hits, tmax=None, normalmap=True, *, albedo=True, normal_depth=True, geometry_normal=True,
+                      material=True):
+        """prt_query_surface: the shading inputs at query_rays' hit records, as a dict of the outputs asked for:
+        albedo [n, 4] and normal_depth [n, 4] as render_aov defines them, geometry_normal [n, 4] (w = 1) and material
+        [n, 8] (base rgb, metalness, emissive rgb, roughness); misses get zeros (normal_depth 0, 0, 0, 1e30).  Pass the
+        tmax the query ran under: record i is a hit iff its t < tmax[i].  hits: intersect()'s numpy records (host
+        path, numpy out) or query_rays' [n, 5] tensor (device path, tensors out, no host wait)."""
+        want = [k for k, on in (("albedo", albedo), ("normal_depth", normal_depth),
+                                ("geometry_normal", geometry_normal), ("material", material)) if on]
+        width = {"albedo": 4, "normal_depth": 4, "geometry_normal": 4, "material": 8}
+        fl = _lib.FLAG_NORMALMAP if normalmap else 0
+        if hasattr(hits, "data_ptr"):
+            import torch
+            n = self._query_tensor(hits, "query_surface: hits", 5)
+            if tmax is not None:
+                self._query_tensor(tmax, "query_surface: tmax", 1, n)
+            out = {k: torch.empty((n, width[k]), dtype=torch.float32, device=hits.device) for k in want}
+            if n:
+                ptrs = [out[k].data_ptr() if k in out else None for k in width]
+                check(self.L.prt_query_surface(self.h, n, hits.data_ptr(), tmax.data_ptr() if tmax is not None else None,
+                                               fl, *ptrs, _lib.OUT_DEVICE))
+            return out
+        rec = np.ascontiguousarray(hits)
+        if rec.dtype.itemsize != 20:
+            raise ValueError("query_surface: hits must be intersect()'s records (20 bytes each)")
+        n = rec.shape[0]
+        tm = _f32(tmax).reshape(-1) if tmax is not None else None
+        if tm is not None and tm.size != n:
+            raise ValueError("query_surface: one tmax per record")
+        out = {k: np.zeros((n, width[k]), F32) for k in want}
+        ptrs = [_ptr(out[k]) if k in out else None for k in width]
+        check(self.L.prt_query_surface(self.h, n, rec.ctypes.data, _ptr(tm), fl, *ptrs, 0))
+        return out
+
     def brdf_probe(self, op, records):
         """prt_brdf_probe: the device BRDF functions on n records (float32 [n, 24] in, [n, 8] out; include/prt.h)."""
         rec = np.ascontiguousarray(records, np.float32).reshape(-1, 24)
