@@ -1,8 +1,9 @@
-// prt_api.cpp -- C-ABI implementation (include/prt.h): the context, device residency of the scene (textures,
-// instances, lights, camera, sky), the queries, the AOVs, the shards.  One host thread per context; all device work
-// on one HIP stream.  The context itself is prt_ctx.h; the mesh entry points (BLAS build, in-place update, skinning,
-// snapshots, read-back) are prt_api_mesh.cpp, the render path (prt_render and what it calls) is prt_api_render.cpp,
-// the image-space passes (denoisers, reprojections) are prt_api_image.cpp.
+// prt_api.cpp -- C-ABI implementation (include/prt.h): the context, device residency of the scene (textures, lights,
+// camera, sky), the pinned staging pool, the queries, the AOVs, the shards.  One host thread per context; all device
+// work on one HIP stream.  The context itself is prt_ctx.h; the mesh entry points (BLAS build, in-place update,
+// skinning, snapshots, read-back) are prt_api_mesh.cpp, the instance entry points and the instance state (records,
+// instance BVH, its updates and rebuilds) are prt_api_instance.cpp, the render path (prt_render and what it calls) is
+// prt_api_render.cpp, the image-space passes (denoisers, reprojections) are prt_api_image.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -11,20 +12,15 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
 
-#include "bvh_build.h"
-#include "bvh_gpu.h"
-#include "prt_blas_cost_gpu.h"
 #include "prt_ctx.h"
 #include "prt_deform.h"
 #include "prt_denoise.h"
-#include "prt_mesh_host.h"
+#include "prt_instance_host.h"
 #include "prt_motion.h"
-#include "prt_tlas_refit_gpu.h"
 
 using namespace prt;
 using namespace prt::host;
@@ -39,9 +35,6 @@ std::string& prt::host::last_error() { return g_err; }
 
 namespace {
 
-// The traversal stacks hold one group per tree level below the root: 8-18 in LDS (by occupancy; 16 in the query
-// kernels), deeper levels in HBM spill columns (ensure_spill), up to tinybvh's 64-entry stack (tiny_bvh.h:6315)
-constexpr int kMaxBvhDepth = 64;
 // tree levels one lane's stack must cover: the deepest BLAS, plus the instance BVH's levels when it is walked
 // (its groups sit below the BLAS's: at most one per TLAS level, the last one the remaining instances of a leaf)
 int stack_depth(const prt_ctx* c) { return c->max_depth + (c->use_tlas ? c->tlas_depth : 0); }
@@ -134,21 +127,41 @@ int prt::host::drain(prt_ctx* c) {
   return wait_stream(c, "waiting for the context's frames");
 }
 
+// waves/SIMD of the persistent traversal kernels for the context's stack depth (prt_instance_host.h occ_at)
+int prt::host::occ_for(const prt_ctx* c) { return occ_at(stack_depth(c)); }
+
 namespace {
-
-// waves/SIMD of the persistent traversal kernels: the LDS stack (9 / 11 / 14 / 18 groups at 7 / 6 / 5 / 4
-// waves) must hold max_depth - 1 groups; deeper BVHs (depth_ok caps them at kMaxBvhDepth = 64 levels) run the
-// 4-wave form with HBM spill columns (ensure_spill)
-int occ_at(int d) {  // the occupancy a stack of d levels allows (7 waves: re-measured best, profiles/r05_occupancy.txt)
-  if (d <= 10) return 7;
-  if (d <= 12) return 6;
-  if (d <= 15) return 5;
-  return 4;
+// a slot's pinned buffer replaced by one of `bytes` (its copies have run: the slot is free)
+int stage_grow(StageSlot& st, size_t bytes) {
+  if (st.p) HIP_TRY(hipHostFree(st.p));
+  st.p = nullptr;
+  st.bytes = 0;
+  HIP_TRY(hipHostMalloc(&st.p, bytes, hipHostMallocDefault));
+  st.bytes = bytes;
+  return PRT_OK;
 }
-
 }  // namespace
 
-int prt::host::occ_for(const prt_ctx* c) { return occ_at(stack_depth(c)); }
+// The staging buffers of an instance set's updates, each of which takes at most `bytes`: the pool filled to
+// kStageSlots slots, the slots' flag words, and every idle slot below `bytes` grown to it -- when the set is first
+// built, so that no later update allocates pinned memory (StageSlot says what that costs).  Nothing to do while the
+// pool is full and was last sized for as much.
+int prt::host::stage_reserve(prt_ctx* c, size_t bytes) {
+  if (c->stage.size() >= kStageSlots && c->stage_bytes >= bytes) return PRT_OK;
+  c->stage_bytes = bytes;
+  for (size_t k = c->stage.size(); k < kStageSlots; k++) c->stage.emplace_back();
+  if (!c->stage_flag) {
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->stage_flag), kStageSlots * 64, hipHostMallocCoherent));
+    std::memset(c->stage_flag, 0, kStageSlots * 64);
+    HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&c->stage_flag_dev), c->stage_flag, 0));
+  }
+  for (StageSlot& t : c->stage) {
+    if (t.used && hipEventQuery(t.ev) == hipSuccess) t.used = false;
+    (void)hipGetLastError();  // (hipErrorNotReady of a buffer still in use)
+    if (!t.used && !t.lost && t.bytes < bytes) PRT_TRY(stage_grow(t, bytes));
+  }
+  return PRT_OK;
+}
 
 // a pinned staging buffer of at least `bytes` (prt_ctx::stage): a free one (its copies have run), a new one while
 // the pool holds fewer than kStageSlots, else the oldest once its copies have run (the only host wait)
@@ -180,13 +193,7 @@ int prt::host::stage_acquire(prt_ctx* c, size_t bytes, StageSlot*& out) {
   }
   pick->seq = ++c->stage_seq;
   StageSlot& st = *pick;
-  if (st.bytes < bytes) {
-    if (st.p) HIP_TRY(hipHostFree(st.p));
-    st.p = nullptr;
-    st.bytes = 0;
-    HIP_TRY(hipHostMalloc(&st.p, bytes, hipHostMallocDefault));
-    st.bytes = bytes;
-  }
+  if (st.bytes < bytes) PRT_TRY(stage_grow(st, bytes));
   if (!st.ev) HIP_TRY(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
   out = &st;
   return PRT_OK;
@@ -198,73 +205,9 @@ int prt::host::stage_release(prt_ctx*, StageSlot& st, hipStream_t s) {
   return PRT_OK;
 }
 
-namespace {
-
-// the refit input of every instance (prt_refit.h) from host transforms xf (16 floats each: the host's inst_xf, or a
-// call's own before it commits them), the mesh boxes and the kinds
-void fill_inst_src(const prt_ctx* c, const float* xf, InstSrc* src) {
-  const int32_t n = (int32_t)c->inst_mesh.size();
-  for (int32_t i = 0; i < n; i++) {
-    InstSrc& s = src[i];
-    const uint32_t m = c->inst_mesh[i];
-    std::memcpy(s.T, xf + 16 * (size_t)i, sizeof(s.T));
-    const MeshHost& mh = c->mesh_info[m];
-    std::memcpy(s.bmin, mh.bmin, sizeof(s.bmin));
-    std::memcpy(s.bmax, mh.bmax, sizeof(s.bmax));
-    s.mesh = m;
-    s.kind = i < (int32_t)c->inst_kind.size() ? c->inst_kind[i] : 0u;
-  }
-}
-
-// prt_ctx::inst_tab: n mesh ids, n kinds, then two float4 per mesh, each part 16-byte aligned
-struct InstTabLayout { size_t kind, box, total; };
-InstTabLayout inst_tab_layout(size_t n, size_t nmesh) {
-  const size_t w = (4 * n + 15) & ~size_t(15);
-  return {w, 2 * w, 2 * w + 32 * nmesh};
-}
-
-// The device buffers of an instance state of n instances: every copy of the ring (frames in flight + 1) and the
-// scratch of prt_update_instances, sized for n (at least the linear-list size; a tree over n instances has at most
-// max(n, 1) nodes), so that later updates never reallocate.  A reallocation frees what queued frames read: it drains
-// first, a host wait.  Only a buffer that is too small is replaced (its contents are lost: a copy that holds the
-// current state is large enough).
-int size_instance_state(prt_ctx* c, int32_t n, bool use_tlas) {
-  if (c->isets.size() < (size_t)c->inflight + 1) c->isets.resize((size_t)c->inflight + 1);
-  const size_t cap = (size_t)std::max(n, kLinearInstances);
-  const size_t cap_nodes = (size_t)std::max(n, 1);
-  const size_t tab = inst_tab_layout(cap, c->mesh_host.size()).total;
-  bool fit = c->inst_tab.bytes >= tab &&
-             (!use_tlas || (c->tlas_order.bytes >= 4 * cap_nodes && c->tlas_box.bytes >= 24 * cap_nodes));
-  for (const InstSet& I : c->isets)
-    fit = fit && I.inst.bytes >= sizeof(InstDev) * cap && I.inst_src.bytes >= sizeof(InstSrc) * cap &&
-          (!use_tlas || (I.tlas8.bytes >= cap_nodes * sizeof(Node8) && I.tlas_slot.bytes >= cap_nodes * 32));
-  if (fit) return PRT_OK;
-  PRT_TRY(drain(c));
-  for (InstSet& I : c->isets) {
-    HIP_TRY(I.inst.ensure(sizeof(InstDev) * cap));
-    HIP_TRY(I.inst_src.ensure(sizeof(InstSrc) * cap));
-    if (use_tlas) {
-      HIP_TRY(I.tlas8.ensure(cap_nodes * sizeof(Node8)));
-      HIP_TRY(I.tlas_slot.ensure(cap_nodes * 32));
-    }
-  }
-  if (c->inst_tab.bytes < tab) {
-    HIP_TRY(c->inst_tab.ensure(tab));
-    c->inst_tab_ok = false;
-  }
-  if (use_tlas) {
-    if (c->tlas_order.bytes < 4 * cap_nodes) {
-      HIP_TRY(c->tlas_order.ensure(4 * cap_nodes));
-      c->tlas_topo = false;
-    }
-    HIP_TRY(c->tlas_box.ensure(24 * cap_nodes));
-  }
-  return PRT_OK;
-}
-
 // `bytes` of host memory into device memory at dst in the context stream's order: copied into a pinned staging
 // buffer now (the caller's memory is free on return), uploaded from there
-int stage_upload(prt_ctx* c, void* dst, const void* src, size_t bytes) {
+int prt::host::stage_upload(prt_ctx* c, void* dst, const void* src, size_t bytes) {
   StageSlot* st = nullptr;
   PRT_TRY(stage_acquire(c, bytes, st));
   st->lost = true;  // until the copy out of it is enqueued (a failure below leaves it out of the pool)
@@ -272,278 +215,6 @@ int stage_upload(prt_ctx* c, void* dst, const void* src, size_t bytes) {
   HIP_TRY(hipMemcpyAsync(dst, st->p, bytes, hipMemcpyHostToDevice, c->stream));
   PRT_TRY(stage_release(c, *st, c->stream));
   st->lost = false;
-  return PRT_OK;
-}
-
-int worker_ok(prt_ctx* c) {
-  if (!c->tlas_worker) return PRT_OK;
-  const TlasWorker::Stats ws = c->tlas_worker->stats();
-  if (ws.failed) return fail(PRT_ERR_HIP, "instance BVH build failed on the worker thread: " + ws.err);
-  return PRT_OK;
-}
-
-// The topology of the instance BVH the device holds (or will hold once the stream has run the queued uploads), once
-// per build: the worker's queue runs empty (a host condition variable, no GPU involved: at most the queued builds),
-// its last tree is what the last upload carries; tree_levels checks every link and orders the nodes by level, and
-// the order goes to tlas_order.  An update's staging buffer holds cap_nodes records of which only these are the
-// tree's: no kernel ever runs over more than tlas_nodes.
-int tlas_topology(prt_ctx* c, int32_t n) {
-  if (c->tlas_topo) return PRT_OK;
-  if (!c->tlas_worker) return fail(PRT_ERR_NOT_READY, "no instance BVH");
-  c->tlas_worker->wait_idle();
-  PRT_TRY(worker_ok(c));
-  std::vector<Node8> nodes;
-  std::vector<uint32_t> slot;
-  c->tlas_worker->last_tree(nodes, slot);
-  const size_t nn = nodes.size();
-  if (!nn || nn > (size_t)std::max(n, 1) || slot.size() != 8 * nn) return fail(PRT_ERR_HIP, "instance BVH: no usable tree");
-  std::vector<uint32_t> ends, order;
-  const char* err = nullptr;
-  if (!tree_levels(nodes.data(), nn, 0u, 0u, (uint32_t)(8 * nn), ends, order, &err))
-    return fail(PRT_ERR_HIP, std::string("instance BVH: ") + err);
-  PRT_TRY(stage_upload(c, c->tlas_order.p, order.data(), 4 * nn));
-  c->tlas_nodes = (uint32_t)nn;
-  c->tlas_level_ends = std::move(ends);
-  c->tlas_topo = true;
-  return PRT_OK;
-}
-
-// What prt_update_instances and prt_rebuild_instances share: the records of the next copy of the instance state
-// (isets[nx]: inst_src, then inst by k_refit) from new transforms, or from the same ones under new kinds or mesh boxes,
-// once the context stream has waited for the frames that read that copy.  xf_host: 16 floats per instance in host
-// memory; xf_dev: packed 4x4 matrices in device memory; both null: the transforms kept in the current copy's inst_src
-// (device-resident transforms; the caller passes the host's inst_xf otherwise).  The instance state is sized, the
-// current copy and icur are left alone: the caller puts a tree into the same copy and commits.
-int next_instance_records(prt_ctx* c, const float* xf_host, const float* xf_dev, size_t& nx_out) {
-  const int32_t n = (int32_t)c->inst_mesh.size();
-  for (int32_t i = 0; i < n; i++)
-    if (c->inst_mesh[i] >= c->mesh_host.size()) return fail(PRT_ERR_INVALID_ARGUMENT, "instance references a missing mesh");
-  PRT_TRY(size_instance_state(c, n, c->use_tlas));
-  const size_t nx = (c->icur + 1) % c->isets.size();
-  InstSet& cur = c->isets[c->icur];
-  InstSet& X = c->isets[nx];
-  for (size_t k = 0; k < X.nuse; k++) HIP_TRY(hipStreamWaitEvent(c->stream, X.uses[k].second, 0));
-  X.nuse = 0;
-  if (xf_host) {  // the records' input filled on the host, as ensure_instances fills it
-    c->inst_stage.resize(n);
-    fill_inst_src(c, xf_host, c->inst_stage.data());
-    PRT_TRY(stage_upload(c, X.inst_src.p, c->inst_stage.data(), sizeof(InstSrc) * (size_t)n));
-    c->inst_tab_ok = false;  // (the table was not brought up to what this refill read)
-  } else {
-    const InstTabLayout L = inst_tab_layout((size_t)std::max(n, kLinearInstances), c->mesh_host.size());
-    if (!c->inst_tab_ok || c->inst_dirty) {  // mesh ids, kinds and the meshes' current root boxes
-      std::vector<char> tab(L.total, 0);
-      std::memcpy(tab.data(), c->inst_mesh.data(), 4 * (size_t)n);
-      if (!c->inst_kind.empty()) std::memcpy(tab.data() + L.kind, c->inst_kind.data(), 4 * std::min((size_t)n, c->inst_kind.size()));
-      for (size_t m = 0; m < c->mesh_info.size(); m++) {
-        std::memcpy(tab.data() + L.box + 32 * m, c->mesh_info[m].bmin, 12);
-        std::memcpy(tab.data() + L.box + 32 * m + 16, c->mesh_info[m].bmax, 12);
-      }
-      PRT_TRY(stage_upload(c, c->inst_tab.p, tab.data(), L.total));
-      c->inst_tab_ok = true;
-    }
-    const char* t = c->inst_tab.as<char>();
-    const InstTabDev tab = {reinterpret_cast<const uint32_t*>(t), reinterpret_cast<const uint32_t*>(t + L.kind),
-                            reinterpret_cast<const float4*>(t + L.box), (uint32_t)c->mesh_host.size()};
-    if (xf_dev) HIP_TRY(launch_inst_src(c->stream, reinterpret_cast<const float4*>(xf_dev), 4u, tab, n, X.inst_src.as<InstSrc>()));
-    else if (&X != &cur) HIP_TRY(launch_inst_src(c->stream, cur.inst_src.as<const float4>(), 6u, tab, n, X.inst_src.as<InstSrc>()));
-    else return fail(PRT_ERR_HIP, "instance update: one copy of the instance state");  // (the ring holds at least two)
-  }
-  HIP_TRY(launch_refit(c->stream, X.inst_src.as<InstSrc>(), n, X.inst.as<InstDev>()));
-  nx_out = nx;
-  return PRT_OK;
-}
-
-// prt_update_instances and, while the transforms are device-resident, every refresh of the instance records: the
-// next copy of the instance state from new transforms (or from the same ones under new kinds or mesh boxes), with the
-// instance BVH refitted over it (prt_tlas_refit.h).  xf_dev: packed 4x4 matrices in device memory; null: the host's
-// inst_xf, or, while prt_ctx::xf_device, the transforms kept in the current copy's inst_src.  Everything is enqueued on
-// the context stream: no host build, no worker job, no wait for the GPU.
-int refit_instances(prt_ctx* c, const float* xf_dev) {
-  const int32_t n = (int32_t)c->inst_mesh.size();
-  const bool use_tlas = c->use_tlas;
-  const bool on_dev = xf_dev || c->xf_device;
-  PRT_TRY(worker_ok(c));
-  for (int32_t i = 0; i < n; i++)
-    if (c->inst_mesh[i] >= c->mesh_host.size()) return fail(PRT_ERR_INVALID_ARGUMENT, "instance references a missing mesh");
-  PRT_TRY(size_instance_state(c, n, use_tlas));
-  if (use_tlas) PRT_TRY(tlas_topology(c, n));
-  size_t nx = 0;
-  PRT_TRY(next_instance_records(c, on_dev ? nullptr : c->inst_xf.data(), xf_dev, nx));
-  InstSet& cur = c->isets[c->icur];
-  InstSet& X = c->isets[nx];
-  if (use_tlas)  // deepest level first, the root last: every child's box is written before its parent reads it
-    for (size_t lv = c->tlas_level_ends.size(); lv-- > 0;) {
-      const uint32_t b = lv ? c->tlas_level_ends[lv - 1] : 0u;
-      HIP_TRY(launch_tlas_refit_level(c->stream, cur.tlas8.as<Node8>(), cur.tlas_slot.as<uint32_t>(), X.tlas8.as<Node8>(),
-                                      X.tlas_slot.as<uint32_t>(), X.inst.as<InstDev>(), (uint32_t)n,
-                                      c->tlas_box.as<float>(), c->tlas_order.as<uint32_t>() + b,
-                                      c->tlas_level_ends[lv] - b, c->tlas_nodes));
-    }
-  c->icur = nx;
-  c->iset_n = n;
-  c->inst_dirty = false;
-  c->tlas_dirty = false;
-  return PRT_OK;
-}
-
-// Instance records on the device (prt_refit.h: MESA inverse, normal matrix, inflated world box): one async copy of
-// the transforms + k_refit on the render stream, so frames already queued keep reading the previous instances.
-// The instance BVH over those boxes (the same refit_instance on the host) is rebuilt for every update, as the
-// reference rebuilds its TLAS every frame (Core/Renderer.cpp:33-41, Core/tiny_bvh.h:1732-1770 BVH::Build over the
-// BLASInstances), by the host SAH build + SAH-optimal collapse: on the calling thread when the instance set changes
-// (its depth sizes the traversal stacks), and for every later update on the context's worker thread, the render
-// stream waiting for that update's build at a host function before its upload (TlasWorker).  The caller only
-// copies the update's transforms; every frame walks the tree built over its own instances.
-int ensure_instances(prt_ctx* c) {
-  if (!c->inst_dirty) return PRT_OK;
-  // device-resident transforms (prt_update_instances with PRT_IN_DEVICE): the host copy is stale; the records come
-  // from the transforms kept on the device, under the new kinds and mesh boxes, and the tree is refitted
-  if (c->xf_device) return refit_instances(c, nullptr);
-  const int32_t n = (int32_t)c->inst_mesh.size();
-  const char* te = std::getenv("PRT_TLAS");  // 1: the instance BVH at any instance count (tests)
-  const bool use_tlas = n > kLinearInstances || (te && std::atoi(te) == 1);
-  // a materials-only update (prt_set_instance_materials) moves no box: the records' kinds are rewritten over
-  // unchanged inverses and boxes, and the instance BVH is left as it is
-  const bool tree_work = use_tlas && (c->tlas_dirty || !c->use_tlas || c->tlas_n != n);
-  const bool async = tree_work && c->use_tlas && c->tlas_n == n && c->tlas_worker;
-  PRT_TRY(worker_ok(c));
-  for (int32_t i = 0; i < n; i++)
-    if (c->inst_mesh[i] >= c->mesh_host.size()) return fail(PRT_ERR_INVALID_ARGUMENT, "instance references a missing mesh");
-  // (filled in ordinary memory and copied into the pinned staging buffer in one memcpy: field-by-field stores into
-  // pinned memory cost ~10 ms per 10,000 instances on the GPU box, profiles/r06_tlas_drift.txt)
-  std::vector<InstSrc>& src = c->inst_stage;
-  src.resize(n);
-  fill_inst_src(c, c->inst_xf.data(), src.data());
-  // the copy of the instance state this update writes: the next one in the ring (frames in flight + 1 copies), once
-  // the context stream has waited for the frames that read it.  Every copy and the scratch of prt_update_instances
-  // are sized here, for n, so that later updates never reallocate
-  PRT_TRY(size_instance_state(c, n, use_tlas));
-  const size_t nx = (c->icur + 1) % c->isets.size();
-  InstSet& cur = c->isets[c->icur];
-  InstSet& X = c->isets[nx];
-  for (size_t k = 0; k < X.nuse; k++) HIP_TRY(hipStreamWaitEvent(c->stream, X.uses[k].second, 0));
-  X.nuse = 0;
-  // a new instance set: its first tree on the calling thread; the stacks are sized for the largest depth that keeps
-  // the traversal's occupancy (and at least the median-split tree's), the cap of the worker's builds
-  BuiltTlas8 tree;
-  int depth_cap = c->tlas_depth;
-  if (tree_work && !async) {
-    std::vector<float> boxes(6 * (size_t)n);
-    for (int32_t i = 0; i < n; i++) {
-      InstDev I;
-      refit_instance(src[i], I);
-      std::memcpy(&boxes[6 * (size_t)i], I.bmin, 12);
-      std::memcpy(&boxes[6 * (size_t)i + 3], I.bmax, 12);
-    }
-    tree = build_tlas8(boxes.data(), n);
-    const int occ = occ_at(c->max_depth + tree.depth);
-    depth_cap = std::max(tree.depth, tlas8_median_depth(n));
-    while (depth_cap < tree.depth + 4 && occ_at(c->max_depth + depth_cap + 1) == occ &&
-           c->max_depth + depth_cap + 1 <= kMaxBvhDepth)
-      depth_cap++;
-  }
-  const size_t cap_nodes = (size_t)std::max(n, 1);  // a tree over n instances has at most max(n, 1) nodes
-  // uploads through one pinned staging slot: the instance sources, then the tree's nodes and slots
-  const size_t sb_src = sizeof(InstSrc) * (size_t)n;
-  const size_t sb_nodes = !tree_work ? 0 : async ? cap_nodes * sizeof(Node8) : tree.nodes.size() * sizeof(Node8);
-  const size_t sb_slot = !tree_work ? 0 : async ? cap_nodes * 32 : tree.slot.size() * 4;
-  const size_t per = sb_src + (use_tlas ? cap_nodes * (sizeof(Node8) + 32) : 0);
-  if (c->stage.size() < kStageSlots || c->stage_bytes < per) {  // the staging buffers this instance set's updates use
-    c->stage_bytes = per;
-    for (size_t k = c->stage.size(); k < kStageSlots; k++) c->stage.emplace_back();
-    if (!c->stage_flag) {
-      HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->stage_flag), kStageSlots * 64, hipHostMallocCoherent));
-      std::memset(c->stage_flag, 0, kStageSlots * 64);
-      HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&c->stage_flag_dev), c->stage_flag, 0));
-    }
-    for (StageSlot& t : c->stage) {
-      if (t.used && hipEventQuery(t.ev) == hipSuccess) t.used = false;
-      (void)hipGetLastError();  // (hipErrorNotReady of a buffer still in use)
-      if (!t.used && !t.lost && t.bytes < per) {
-        if (t.p) HIP_TRY(hipHostFree(t.p));
-        t.p = nullptr;
-        t.bytes = 0;
-        HIP_TRY(hipHostMalloc(&t.p, per, hipHostMallocDefault));
-        t.bytes = per;
-      }
-    }
-  }
-  StageSlot* st = nullptr;
-  PRT_TRY(stage_acquire(c, sb_src + sb_nodes + sb_slot, st));
-  char* hp = static_cast<char*>(st->p);
-  st->lost = true;  // until the copies out of it are enqueued (a failure below leaves it out of the pool)
-  std::memcpy(hp, src.data(), sb_src);  // (the worker reads the sources from here)
-  HIP_TRY(hipMemcpyAsync(X.inst_src.p, hp, sb_src, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(launch_refit(c->stream, X.inst_src.as<InstSrc>(), n, X.inst.as<InstDev>()));
-  if (tree_work) {
-    char* q = hp + sb_src;
-    if (async) {  // the worker writes the tree into q; the stream's upload waits for it
-      const size_t k = (size_t)(st - c->stage.data());  // this buffer's flag word (free with the buffer)
-      auto job = std::make_shared<TlasJob>();
-      job->src = reinterpret_cast<const InstSrc*>(hp);
-      job->n = n;
-      job->dst = q;
-      job->cap = cap_nodes;
-      job->max_depth = c->tlas_depth;
-      job->flag = c->stage_flag + 16 * k;
-      __atomic_store_n(job->flag, 0u, __ATOMIC_RELAXED);
-      HIP_TRY(launch_wait_host(c->stream, c->stage_flag_dev + 16 * k, c->diag.as<uint32_t>() + 2, kHostWaitLimitS));
-      c->tlas_worker->submit(job);
-    } else {
-      std::memcpy(q, tree.nodes.data(), sb_nodes);
-      std::memcpy(q + sb_nodes, tree.slot.data(), sb_slot);
-    }
-    HIP_TRY(hipMemcpyAsync(X.tlas8.p, q, sb_nodes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(X.tlas_slot.p, q + sb_nodes, sb_slot, hipMemcpyHostToDevice, c->stream));
-  } else if (use_tlas && &X != &cur) {  // a materials-only update: the current tree, into this copy
-    HIP_TRY(hipMemcpyAsync(X.tlas8.p, cur.tlas8.p, cap_nodes * sizeof(Node8), hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(X.tlas_slot.p, cur.tlas_slot.p, cap_nodes * 32, hipMemcpyDeviceToDevice, c->stream));
-  }
-  PRT_TRY(stage_release(c, *st, c->stream));
-  st->lost = false;
-  c->use_tlas = use_tlas;
-  if (!use_tlas) {
-    c->tlas_depth = 0;
-    c->tlas_n = -1;
-  } else if (tree_work && !async) {  // a new instance set
-    if (!c->tlas_worker) c->tlas_worker.reset(new TlasWorker());
-    c->tlas_worker->seed(tree);
-    c->tlas_depth = depth_cap;
-    c->tlas_rebuilds = c->tlas_async = 0;
-    c->tlas_n = n;
-  } else if (async) {
-    c->tlas_rebuilds++;
-    c->tlas_async++;
-  }
-  c->icur = nx;
-  c->iset_n = n;
-  c->inst_tab_ok = false;            // (a device-side refill uploads what this one read)
-  if (tree_work) c->tlas_topo = false;  // a new tree: the next prt_update_instances takes its topology
-  c->inst_dirty = false;
-  c->tlas_dirty = false;
-  return PRT_OK;
-}
-
-}  // namespace
-
-// a frame enqueued on stream st reads the current copy of the instance state: the next update that rewrites it
-// waits for this point of st (InstSet)
-int prt::host::record_inst_use(prt_ctx* c, hipStream_t st) {
-  InstSet& I = c->isets[c->icur];
-  for (size_t k = 0; k < I.nuse; k++)
-    if (I.uses[k].first == st) {
-      HIP_TRY(hipEventRecord(I.uses[k].second, st));
-      return PRT_OK;
-    }
-  if (I.nuse == I.uses.size()) {
-    hipEvent_t e = nullptr;
-    HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    I.uses.push_back({st, e});
-  }
-  I.uses[I.nuse].first = st;
-  HIP_TRY(hipEventRecord(I.uses[I.nuse].second, st));
-  I.nuse++;
   return PRT_OK;
 }
 
@@ -792,237 +463,6 @@ int prt_set_textures(prt_ctx* c, const prt_texture* t, int32_t n) {
   c->tex_host = host;
   PRT_FOR_MEMBERS(prt_set_textures(m, t, n));
   return PRT_OK;
-}
-
-int prt_set_instances(prt_ctx* c, const float* xf, const uint32_t* mi, int32_t n) {
-  if (!c || !xf || !mi || n <= 0) return fail(PRT_ERR_INVALID_ARGUMENT, "bad instances");
-  // (no join of the frames in flight: the update writes the next copy of the instance state, InstSet)
-  if (n > kMaxInstances) return fail(PRT_ERR_UNSUPPORTED, "more than 2^24 instances");
-  c->inst_xf.assign(xf, xf + 16 * (size_t)n);
-  if ((size_t)n != c->inst_mesh.size()) c->inst_kind.clear();  // materials survive transform updates only
-  c->inst_mesh.assign(mi, mi + n);
-  c->xf_device = false;  // the host copy is current again (prt_update_instances with device transforms made it stale)
-  c->inst_dirty = true;
-  c->tlas_dirty = true;
-  c->shade_epoch++;
-  c->inst_epoch++;  // transforms, boxes, the instance BVH and the hit word's instance bits: kept primary hits are stale
-  HIP_TRY(hipSetDevice(c->device));
-  if (!c->mesh_host.empty()) {
-    PRT_TRY(ensure_instances(c));
-  }
-  PRT_FOR_MEMBERS(prt_set_instances(m, xf, mi, n));
-  return PRT_OK;
-}
-
-int prt_set_instance_materials(prt_ctx* c, const int32_t* kinds, int32_t n) {
-  if (!c) return fail(PRT_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  // (no join of the frames in flight: the update writes the next copy of the instance state, InstSet)
-  if (n == 0 || !kinds) {
-    c->inst_kind.clear();
-  } else {
-    if (n != (int32_t)c->inst_mesh.size()) return fail(PRT_ERR_INVALID_ARGUMENT, "one material kind per instance");
-    for (int32_t i = 0; i < n; i++)
-      if (kinds[i] < PRT_MAT_TEXTURED || kinds[i] > PRT_MAT_MIRROR) return fail(PRT_ERR_INVALID_ARGUMENT, "bad material kind");
-    c->inst_kind.assign(kinds, kinds + n);
-  }
-  // No inst_epoch bump: a kept primary hit is (t, u, v, prim | inst << pbits), and a materials-only update moves no
-  // transform, box or tree (ensure_instances) and leaves pbits alone; the kind is read at shading, from the
-  // instance record.  Dielectric kinds switch to the extension kernels, which neither read nor write phit.
-  c->shade_epoch++;  // ... but a kept primary surface holds the material the kind shaped
-  c->inst_dirty = true;
-  HIP_TRY(hipSetDevice(c->device));
-  if (!c->mesh_host.empty() && !c->inst_mesh.empty()) {
-    PRT_TRY(ensure_instances(c));
-  }
-  PRT_FOR_MEMBERS(prt_set_instance_materials(m, kinds, n));
-  return PRT_OK;
-}
-
-int prt_update_instances(prt_ctx* c, const float* xf, int32_t n, uint32_t in_flags) {
-  if (!c || !xf) return fail(PRT_ERR_INVALID_ARGUMENT, "bad instance update arguments");
-  if (in_flags & ~PRT_IN_DEVICE) return fail(PRT_ERR_INVALID_ARGUMENT, "unknown input flags");
-  if (c->mesh_host.empty()) return fail(PRT_ERR_NOT_READY, "no meshes: call prt_set_meshes");
-  if (c->inst_mesh.empty()) return fail(PRT_ERR_NOT_READY, "no instances: call prt_set_instances");
-  if (n != (int32_t)c->inst_mesh.size())
-    return fail(PRT_ERR_INVALID_ARGUMENT, "instance update: the instance count must stay (a new set needs prt_set_instances)");
-  const bool dev_in = (in_flags & PRT_IN_DEVICE) != 0;
-  if (dev_in && c->sh_kind == 2) return fail(PRT_ERR_UNSUPPORTED, "device transforms on a local shard group");
-  if (dev_in && (reinterpret_cast<uintptr_t>(xf) & 15u))
-    return fail(PRT_ERR_INVALID_ARGUMENT, "device transforms must be 16-byte aligned");
-  PRT_TRY(worker_ok(c));
-  // (no join of the frames in flight: the update writes the next copy of the instance state, InstSet)
-  HIP_TRY(hipSetDevice(c->device));
-  if (!dev_in) {
-    c->inst_xf.assign(xf, xf + 16 * (size_t)n);
-    c->xf_device = false;
-  }
-  const bool first = c->iset_n != n;
-  if (first) {  // the set was never brought to the device (prt_set_instances came before the meshes): its first
-    c->inst_dirty = true;  // build, from the host's transforms; device transforms then move it
-    c->tlas_dirty = true;
-    PRT_TRY(ensure_instances(c));
-  }
-  if (dev_in || !first) PRT_TRY(refit_instances(c, dev_in ? xf : nullptr));
-  if (dev_in) c->xf_device = true;
-  c->shade_epoch++;
-  c->inst_epoch++;  // transforms, boxes and the instance BVH changed: kept primary hits and light visibility are stale
-  PRT_FOR_MEMBERS(prt_update_instances(m, xf, n, in_flags));
-  return PRT_OK;
-}
-
-int prt_rebuild_instances(prt_ctx* c, const float* xf, int32_t n, uint32_t in_flags, int32_t builder) {
-  if (!c) return fail(PRT_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  if (builder == PRT_BUILDER_HOST_SAH || builder == PRT_BUILDER_HOST_SBVH)
-    return fail(PRT_ERR_UNSUPPORTED, "instance rebuild: the host builders rebuild through prt_set_instances only");
-  if (builder != PRT_BUILDER_GPU_LBVH && builder != PRT_BUILDER_GPU_PLOC)
-    return fail(PRT_ERR_INVALID_ARGUMENT, "bad instance BVH builder");
-  if (in_flags & ~PRT_IN_DEVICE) return fail(PRT_ERR_INVALID_ARGUMENT, "unknown input flags");
-  if (!xf && in_flags) return fail(PRT_ERR_INVALID_ARGUMENT, "instance rebuild without transforms takes no input flags");
-  if (c->mesh_host.empty()) return fail(PRT_ERR_NOT_READY, "no meshes: call prt_set_meshes");
-  if (c->inst_mesh.empty()) return fail(PRT_ERR_NOT_READY, "no instances: call prt_set_instances");
-  if (n != (int32_t)c->inst_mesh.size())
-    return fail(PRT_ERR_INVALID_ARGUMENT, "instance rebuild: the instance count must stay (a new set needs prt_set_instances)");
-  const bool dev_in = xf && (in_flags & PRT_IN_DEVICE) != 0;
-  if (dev_in && c->sh_kind == 2) return fail(PRT_ERR_UNSUPPORTED, "device transforms on a local shard group");
-  if (dev_in && (reinterpret_cast<uintptr_t>(xf) & 15u))
-    return fail(PRT_ERR_INVALID_ARGUMENT, "device transforms must be 16-byte aligned");
-  PRT_TRY(worker_ok(c));
-  // (no join of the frames in flight: the rebuild writes the next copy of the instance state, InstSet)
-  HIP_TRY(hipSetDevice(c->device));
-  if (c->iset_n != n) {  // the set was never brought to the device (prt_set_instances came before the meshes): its
-    c->inst_dirty = true;  // first build, from the host's transforms, decides between the list and the tree
-    c->tlas_dirty = true;
-    PRT_TRY(ensure_instances(c));
-  }
-  if (!c->use_tlas) {  // the linear list has no tree: the call is prt_update_instances (every member included)
-    if (!xf) return PRT_OK;
-    return prt_update_instances(c, xf, n, in_flags);
-  }
-  const size_t N = (size_t)n;
-  if (c->tb_fat.bytes < 48 * N || c->tb_nodes.bytes < sizeof(Node8) * N || c->tb_tris.bytes < sizeof(TriMT) * N) {
-    PRT_TRY(wait_stream(c, "prt_rebuild_instances"));  // (an earlier rebuild's kernels read the scratch this frees)
-    HIP_TRY(c->tb_fat.ensure(48 * N));
-    HIP_TRY(c->tb_nodes.ensure(sizeof(Node8) * N));
-    HIP_TRY(c->tb_tris.ensure(sizeof(TriMT) * N));
-  }
-  // The next copy's records, then the builder's input from their boxes.  Nothing the frames read changes before the
-  // commit below: a failure from here on leaves a half-written copy that is not the current one.
-  size_t nx = 0;
-  PRT_TRY(next_instance_records(c, dev_in ? nullptr : xf ? xf : c->xf_device ? nullptr : c->inst_xf.data(),
-                                dev_in ? xf : nullptr, nx));
-  InstSet& X = c->isets[nx];
-  HIP_TRY(launch_tlas_prims(c->stream, X.inst.as<InstDev>(), n, c->tb_fat.as<float4>()));
-  // The build, into the context's scratch.  The builder synchronises the context stream once per PLOC iteration and
-  // once per tree level; the wait before it is the bounded one of an RCCL context.
-  PRT_TRY(wait_stream(c, "prt_rebuild_instances"));
-  GpuBlasInfo gi = {};
-  std::vector<uint32_t> ends;
-  const hipError_t be = gpu_build_blas8(c->stream, c->tb_fat.as<float>(), n, /*max_leaf*/ 1, c->tb_nodes.as<Node8>(),
-                                        c->tb_tris.as<TriMT>(), &gi, builder == PRT_BUILDER_GPU_PLOC, &ends);
-  if (be != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(PRT_ERR_HIP, std::string("instance rebuild: the device build failed: ") + hipGetErrorString(be));
-  }
-  bool ok = gi.nodes >= 1 && gi.nodes <= (uint32_t)n && gi.tris == (uint32_t)n && gi.depth >= 1 &&
-            ends.size() == (size_t)gi.depth && ends.back() == gi.nodes;
-  for (size_t d = 1; ok && d < ends.size(); d++) ok = ends[d] > ends[d - 1];
-  if (!ok) return fail(PRT_ERR_HIP, "instance rebuild: the device build returned no usable tree");
-  if (const char* tr = std::getenv("PRT_REBUILD_TRACE"); tr && std::atoi(tr) == 1)  // (scripts/instance_rebuild_time.py)
-    std::fprintf(stderr, "prt_rebuild_instances: %d instances, %s: %u nodes, %d levels, the builder waited for the stream %u times\n",
-                 n, builder == PRT_BUILDER_GPU_PLOC ? "GPU_PLOC" : "GPU_LBVH", gi.nodes, gi.depth, gi.syncs);
-  if (c->max_depth + gi.depth > kMaxBvhDepth)
-    return fail(PRT_ERR_UNSUPPORTED, "instance rebuild: the new instance BVH is deeper than the traversal stacks cover");
-  // The commit, in the context stream's order: the tree as an instance BVH into the next copy, the level order of a
-  // later refit (the builder emits level d as [ends[d - 1], ends[d]): the identity), then the host's view of it
-  // (the builder is through with its input: the fat triangles' 48 bytes per instance are the 12 per node of the order)
-  HIP_TRY(launch_tlas_finish(c->stream, c->tb_nodes.as<Node8>(), c->tb_tris.as<TriMT>(), gi.tris, gi.nodes, (uint32_t)n,
-                             ends.data(), ends.size(), c->tb_fat.as<uint32_t>(), X.tlas8.as<Node8>(),
-                             X.tlas_slot.as<uint32_t>()));
-  std::vector<uint32_t> order(gi.nodes);
-  for (uint32_t j = 0; j < gi.nodes; j++) order[j] = j;
-  PRT_TRY(stage_upload(c, c->tlas_order.p, order.data(), 4 * (size_t)gi.nodes));
-  c->tlas_nodes = gi.nodes;
-  c->tlas_level_ends = std::move(ends);
-  c->tlas_topo = true;  // (prt_read_tlas / prt_tlas_cost and the next refit never ask the worker for its stale tree)
-  // a deeper tree than the stacks were sized for: they are sized from stack_depth(c) at every launch
-  if (gi.depth > c->tlas_depth) c->tlas_depth = gi.depth;
-  c->icur = nx;
-  c->iset_n = n;
-  c->inst_dirty = false;
-  c->tlas_dirty = false;
-  if (xf && !dev_in) {
-    c->inst_xf.assign(xf, xf + 16 * N);
-    c->xf_device = false;
-  }
-  if (dev_in) c->xf_device = true;
-  c->shade_epoch++;
-  c->inst_epoch++;  // transforms, boxes and the instance BVH changed: kept primary hits and light visibility are stale
-  PRT_FOR_MEMBERS(prt_rebuild_instances(m, xf, n, in_flags, builder));
-  return PRT_OK;
-}
-
-namespace {
-// the instance state as the next frame reads it, and the live tree's node count (0: the rays walk the linear list)
-int tlas_current(prt_ctx* c, uint32_t& n_nodes) {
-  if (c->mesh_host.empty()) return fail(PRT_ERR_NOT_READY, "no meshes: call prt_set_meshes");
-  if (c->inst_mesh.empty()) return fail(PRT_ERR_NOT_READY, "no instances: call prt_set_instances");
-  PRT_JOIN(c);  // frames in flight complete first (prt_set_frames_in_flight)
-  HIP_TRY(hipSetDevice(c->device));
-  PRT_TRY(ensure_instances(c));
-  n_nodes = 0;
-  if (!c->use_tlas) return PRT_OK;
-  if (c->tlas_topo) {
-    n_nodes = c->tlas_nodes;
-  } else {  // the worker's last tree is the one the stream uploads last (tlas_topology)
-    if (!c->tlas_worker) return fail(PRT_ERR_NOT_READY, "no instance BVH");
-    c->tlas_worker->wait_idle();
-    PRT_TRY(worker_ok(c));
-    n_nodes = (uint32_t)c->tlas_worker->last_tree_nodes();
-  }
-  return PRT_OK;
-}
-}  // namespace
-
-int prt_tlas_cost(prt_ctx* c, double* cost) {
-  if (!c) return fail(PRT_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  if (!cost) return fail(PRT_ERR_INVALID_ARGUMENT, "cost is NULL");
-  uint32_t nn = 0;
-  PRT_TRY(tlas_current(c, nn));
-  if (!nn) {
-    *cost = 0.0;
-    return PRT_OK;
-  }
-  const size_t slots = (size_t)blas_cost_blocks(nn) + 2;  // the blocks' sums, the root area, the result
-  if (c->cost_part.bytes < 8 * slots) {
-    PRT_TRY(wait_stream(c, "prt_tlas_cost"));  // (an earlier call's kernels were waited for; a larger tree)
-    HIP_TRY(c->cost_part.ensure(8 * slots));
-  }
-  double* part = c->cost_part.as<double>();
-  double* out = part + (slots - 1);
-  HIP_TRY(launch_blas_cost(c->stream, c->isets[c->icur].tlas8.as<Node8>(), nn, part, out));
-  double v = 0.0;
-  HIP_TRY(hipMemcpyAsync(&v, out, 8, hipMemcpyDeviceToHost, c->stream));
-  PRT_TRY(wait_stream(c, "prt_tlas_cost"));
-  *cost = v;
-  return PRT_OK;
-}
-
-int prt_read_tlas(prt_ctx* c, void* nodes, uint64_t node_bytes, uint32_t* slots, uint64_t slot_bytes,
-                  uint64_t* nodes_needed, uint64_t* slots_needed) {
-  if (!c) return fail(PRT_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  uint32_t nn = 0;
-  PRT_TRY(tlas_current(c, nn));
-  const uint64_t nb = (uint64_t)nn * sizeof(Node8), sb = (uint64_t)nn * 32;
-  if (nodes_needed) *nodes_needed = nb;
-  if (slots_needed) *slots_needed = sb;
-  if (!nodes || !slots) return PRT_OK;
-  if (node_bytes < nb || slot_bytes < sb) return fail(PRT_ERR_INVALID_ARGUMENT, "prt_read_tlas: buffer too small");
-  if (nn) {
-    const InstSet& I = c->isets[c->icur];
-    HIP_TRY(hipMemcpyAsync(nodes, I.tlas8.p, nb, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(slots, I.tlas_slot.p, sb, hipMemcpyDeviceToHost, c->stream));
-  }
-  return wait_stream(c, "prt_read_tlas");
 }
 
 int prt_set_area_lights(prt_ctx* c, const prt_area_light* a, int32_t n) {

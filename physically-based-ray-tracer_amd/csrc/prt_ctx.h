@@ -1,5 +1,6 @@
-// prt_ctx.h -- the context (struct prt_ctx) and what the host translation units of the C ABI share: error
-// reporting, device buffers, the context's parts, and the helpers the image-space passes call.  Internal.
+// prt_ctx.h -- the context (struct prt_ctx) and what the host translation units of the C ABI (prt_api.cpp,
+// prt_api_mesh.cpp, prt_api_instance.cpp, prt_api_render.cpp, prt_api_image.cpp, prt_api_query.cpp) share: error
+// reporting, device buffers, the context's parts, and the helpers they call across files.  Internal.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -125,7 +126,7 @@ struct Flight {
 };
 
 // one pinned staging buffer of ensure_instances' uploads (prt_ctx::stage): reused once its copies have run.  The
-// kStageSlots buffers are allocated when an instance set is first built (pinned allocation in the update path cost
+// kStageSlots buffers are allocated when an instance set is first built (stage_reserve: pinned allocation in the update path cost
 // 20-190 ms per buffer on the GPU box, profiles/r06_tlas_drift.txt); an update that finds all of them in use waits
 // for the oldest one's copies (the host at most kStageSlots updates ahead of the GPU)
 constexpr size_t kStageSlots = 8;
@@ -228,7 +229,8 @@ struct prt_ctx {
   // instance BVH (more than kLinearInstances instances, or PRT_TLAS=1), rebuilt for every prt_set_instances as the
   // reference rebuilds its TLAS every frame (Core/Renderer.cpp:33-41, Core/tiny_bvh.h:1732-1770): the host SAH
   // build + SAH-optimal collapse (bvh_build.h build_tlas8), on the calling thread when the instance set changes,
-  // on the worker thread (tlas_worker) in stream order for every later update (ensure_instances)
+  // on the worker thread (tlas_worker) for every later update, the stream waiting for that build in a one-lane
+  // kernel before the tree's upload (prt_api_instance.cpp ensure_instances; TlasWorker says why no host function)
   bool use_tlas = false;
   int tlas_depth = 0;    // levels the traversal stacks are sized for (>= the current tree's depth)
   int32_t tlas_n = -1;   // instance count of the current tree (-1: none)
@@ -363,14 +365,22 @@ struct prt_ctx {
 namespace prt::host {
 
 // prt_api.cpp: the context stream waits for the frames in flight (every entry point but an in-flight prt_render
-// starts with it); a pinned staging buffer (prt_ctx::stage) and its return once the copies out of it are enqueued
+// starts with it); a pinned staging buffer (prt_ctx::stage) and its return once the copies out of it are enqueued;
+// the pool allocated ahead for uploads of up to `bytes` (stage_reserve); host memory into device memory through one
+// staging buffer, in the context stream's order (stage_upload)
 int join_flights(prt_ctx* c);
 #define PRT_JOIN(ctx) PRT_TRY(::prt::host::join_flights(ctx))
 int stage_acquire(prt_ctx* c, size_t bytes, StageSlot*& out);
 int stage_release(prt_ctx*, StageSlot& st, hipStream_t s);
+int stage_reserve(prt_ctx* c, size_t bytes);
+int stage_upload(prt_ctx* c, void* dst, const void* src, size_t bytes);
+// prt_api_instance.cpp: the device instance state brought up to the host's instances, when it is out of date
+// (scene_ready calls it before every frame); the mark of a frame's read of the instance state
+int ensure_instances(prt_ctx* c);
+int record_inst_use(prt_ctx* c, hipStream_t st);
 // prt_api.cpp, for the render path: finish the queued frames before resident buffers are overwritten or freed; the
 // bounded RCCL waits; the traversal occupancy and whether the stacks cover the BVH; the HBM spill columns of S; the
-// scene as the kernels get it; the screen pass's parameters; the mark of a frame's read of the instance state
+// scene as the kernels get it; the screen pass's parameters
 int drain(prt_ctx* c);
 ncclResult_t rccl_settle(const Rccl* R, ncclComm_t comm, ncclResult_t r);
 int rccl_wait(prt_ctx* c, hipStream_t s, const char* what);
@@ -379,8 +389,7 @@ bool depth_ok(const prt_ctx* c);
 int ensure_spill(prt_ctx* c, SceneDev& S, size_t threads);
 int scene_ready(prt_ctx* c, SceneDev& S);
 PostDev post_params(const prt_ctx* c, int32_t W, int32_t H);
-int record_inst_use(prt_ctx* c, hipStream_t st);
-// prt_api.cpp, for the mesh entry points (prt_api_mesh.cpp): wait for the context stream (bounded on an RCCL-sharded
+// prt_api.cpp, for the mesh and instance entry points (prt_api_mesh.cpp, prt_api_instance.cpp): wait for the context stream (bounded on an RCCL-sharded
 // context, as drain())
 int wait_stream(prt_ctx* c, const char* what);
 // a setter of a local group applies to every member (member 0 = the group context itself)

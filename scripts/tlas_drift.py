@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Instance-BVH drift: N tori drift across the field for F frames (every instance moved
 before every frame, wrapping at the field's edge; 1280x720, 2 spp, depth 3), under the library's policy
-(prt_api.cpp ensure_instances: a host SAH build for every update, on the context's worker thread, the stream waiting
+(prt_api_instance.cpp ensure_instances: a host SAH build for every update, on the context's worker thread, the stream waiting
 for each update's build before its upload).
 
 The frames are paced as a render loop presenting them would: at most PACE (env PRT_DRIFT_PACE, default 3; 0: no

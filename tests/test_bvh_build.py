@@ -292,7 +292,7 @@ def test_tlas_invariants(checker, tmp_path):
 
 @pytest.mark.parametrize("n", [1, 2, 9, 65, 1000, 5000])
 def test_tlas_depth_cap_and_median_fallback(checker, tmp_path, n):
-    """build_tlas8's depth cap (prt_api.cpp ensure_instances sizes the traversal stacks at an instance count's first
+    """build_tlas8's depth cap (prt_api_instance.cpp ensure_instances sizes the traversal stacks at an instance count's first
     build and caps the worker's later builds there): a cap at the SAH tree's own depth keeps the SAH tree; a cap
     below it yields the balanced median-split tree, within tlas8_median_depth(n) levels; both keep every instance in
     exactly one slot, inside its slot's box, and at most max(n, 1) nodes."""
