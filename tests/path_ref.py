@@ -32,6 +32,9 @@ sampling made (pb of the hit it left, pl = d^2 / (area cos_l) with d measured fr
 mirror's ray and a dielectric's children.  Shadow rays do not see the light.  Shading normals are the rectangles' own,
 never flipped: a back-face hit is shaded with N.V < 0 exactly as the closed forms take it.
 
+An instance transform may be rigid (Scene, Rect.carried): the rectangle and its normal are carried to the world, where
+everything above happens.  Unit normals stay required: lobe_densities and the MIS weights assume them.
+
 Random numbers are numpy's, so only the estimator's expectation and variance are comparable with an implementation,
 never single frames.  `slip=` plants one named defect (SLIPS) to show that a comparison against this reference has the
 power to see it.
@@ -47,7 +50,7 @@ _LUM = np.array([0.2126, 0.7152, 0.0722])                # luminance(), Core/BRD
 
 SLIPS = ("no_lobe_division", "direct_not_scaled_by_throughput", "indirect_miss_is_black",
          "emission_only_at_first_hit", "cap_one_early", "cap_one_late", "spec_below_horizon_ends_path",
-         "last_segment_weighted_everywhere", "glass_children_swapped")
+         "last_segment_weighted_everywhere", "glass_children_swapped", "bounced_ray_not_transformed")
 
 
 def _unit0(v):
@@ -68,8 +71,21 @@ class Rect:
         self.metal = float(np.asarray(mat["metalness"]).reshape(()))
         self.rough = float(np.asarray(mat["roughness"]).reshape(()))
         self.emis = np.asarray(mat["emissive"], np.float64).reshape(3)
-        if kind == MAT_MIRROR:                               # prt.h: MIRROR forces metalness 1 / roughness 0
-            self.metal, self.rough = 1.0, 0.0
+        if kind == MAT_MIRROR:                               # prt.h: MIRROR forces metalness 1 / roughness 0, and
+            self.metal, self.rough = 1.0, 0.0                # Core/Scene.cpp:199-204 never sets a mirror's emission
+            self.emis = np.zeros(3)
+        self.N_object = self.N                               # the normal as authored, before carried()
+
+    def carried(self, T):
+        """This rectangle under the rigid instance transform T (4x4, row-major): c' = T c, eu' = R eu, ev' = R ev,
+        N' = R N -- a rotation's normal matrix is the rotation."""
+        T = np.asarray(T, np.float64)
+        Rm = T[:3, :3]
+        assert np.array_equal(T[3], [0.0, 0.0, 0.0, 1.0]) and np.abs(Rm.T @ Rm - np.eye(3)).max() <= 1e-6, T
+        self.c, self.eu, self.ev = Rm @ self.c + T[:3, 3], Rm @ self.eu, Rm @ self.ev
+        self.plane = np.cross(self.eu, self.ev)
+        self.N = Rm @ self.N_object
+        return self
 
     def hit(self, O, D, margin=None):
         """t (inf where none) of rays O, D with 0 < t; with `margin` also whether the plane point lies within that
@@ -94,7 +110,9 @@ def _rect_of_mesh(mesh, textures, kind):
     v = np.asarray(mesh.vertices, np.float64).reshape(-1, 3)
     assert v.shape[0] == 6 and np.array_equal(v[1], v[4]) and np.array_equal(v[2], v[3])
     c, eu, ev = v[0], v[1] - v[0], v[2] - v[0]
-    assert np.allclose(v[5], c + eu + ev, atol=1e-12) and abs(eu @ ev) < 1e-12
+    # (a mesh authored pre-rotated holds float32 roundings of a rectangle's corners)
+    scale = np.linalg.norm(eu) * np.linalg.norm(ev)
+    assert np.allclose(v[5], c + eu + ev, atol=1e-6 * np.sqrt(scale)) and abs(eu @ ev) < 1e-6 * scale
     n = np.asarray(mesh.fixed_normals, np.float64).reshape(-1, 4)[:, :3]
     assert (n == n[0]).all() and np.isclose(np.linalg.norm(n[0]), 1.0)
     mat = R.material(mesh, textures, np.zeros(1, np.int64), np.full(1, 0.25, R.F), np.full(1, 0.25, R.F))
@@ -102,15 +120,15 @@ def _rect_of_mesh(mesh, textures, kind):
 
 
 class Scene:
-    """The rectangles, lights, sky and area light of a scenes.SceneData-shaped object (identity instances, one per
-    mesh in order) under the flags `stochastic`, `skybox` and `lighted`."""
+    """The rectangles, lights, sky and area light of a scenes.SceneData-shaped object (one instance per mesh in order,
+    each under a rigid transform: R^T R = I within 1e-6 and any translation; anything else asserts) under the flags
+    `stochastic`, `skybox` and `lighted`."""
 
     def __init__(self, sd, stochastic=False, skybox=True, lighted=True):
         kinds = sd.materials if sd.materials is not None else [MAT_TEXTURED] * len(sd.instances)
         self.rects = []
         for k, (mi, T) in enumerate(sd.instances):
-            assert np.array_equal(np.asarray(T), np.eye(4))
-            self.rects.append(_rect_of_mesh(sd.meshes[mi], sd.textures, int(kinds[k])))
+            self.rects.append(_rect_of_mesh(sd.meshes[mi], sd.textures, int(kinds[k])).carried(T))
         self.lights, self.sky, self.sd = sd.lights, sd.sky, sd
         self.stochastic, self.skybox, self.lighted = stochastic, skybox and sd.sky is not None, lighted
         self.light = None
@@ -299,7 +317,7 @@ class _Run:
     def shade(self, r, I, D, depth, acc):
         s, n = self.s, len(I)
         V = -D
-        N = np.broadcast_to(r.N, (n, 3))
+        N = np.broadcast_to(r.N_object if self.slip == "bounced_ray_not_transformed" and depth > 0 else r.N, (n, 3))
         base = np.broadcast_to(r.base, (n, 3))
         metal, rough = np.full(n, r.metal), np.full(n, r.rough)
         last = depth == self.bounces - 1

@@ -21,6 +21,11 @@ sky), built from its floor_scene / _flat_quad / sky_ramp and test_gpu_scene_quer
                     test_gpu_estimator over the floor; bounces 3: MIS at depth 0 and 1, an unweighted last segment at
                     depth 2, BRDF rays from the wall reaching the light; and bounces 1, where the first hit is the
                     last segment (the planted slip of a weighted last segment shows there, see test_path_ref.py)
+  corner-turned     the corner (plain and stochastic lights) with instances, camera and lights under one rigid motion
+                    G, a rotation about a generic axis and a translation; mesh k is authored rotated by Q_k^-1 and
+                    instanced with G Q_k, so every instance has its own rotation and no world normal is axis-aligned
+                    (path_ref carries rectangles under rigid transforms); bounces 3 with and without the stochastic
+                    flag.  The sky does not turn and the camera's up stays (0, 1, 0): another scene, not another view
   glass-over-floor  a DIELECTRIC quad over part of the floor, whose emission texel is lit, under sky_ramp(), seen from
                     steeply above (GLASS_CAM); bounces 3 and 4: the refracted child shades the floor, whose bounce
                     meets the glass's back face
@@ -41,7 +46,7 @@ A pixel whose reference sigma is 0 (a shadowed pixel at bounces 1) must equal th
 The largest z (deviation over sigma sqrt(1 / n + 1 / M); the bound is 6) seen on the oracle, whose frames the device
 reproduces bit for bit (test_device_equals_oracle), and the reference's run time are recorded in
 tests/test_path_ref.py; on an MI355X every case printed the oracle's sums and z to the last digit, largest pixel 3.05
-(corner-area, bounces 3), largest sum 1.95 (sky-floor (0.5, 0.5)), 1 to 2.3 s per test.
+(corner-area, bounces 3), largest sum 2.17 (corner-turned-plain; 1.95 on sky-floor (0.5, 0.5)), 1 to 2.3 s per test.
 """
 import functools
 
@@ -113,6 +118,47 @@ def corner_scene(variant):
                             "corner-" + variant, materials=kinds, area_light=light)
 
 
+def _rotation(axis, angle):
+    """Rodrigues' rotation about `axis` by `angle`, float64 3 x 3."""
+    a = np.asarray(axis, np.float64) / np.linalg.norm(axis)
+    K = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+    return np.eye(3) + np.sin(angle) * K + (1.0 - np.cos(angle)) * (K @ K)
+
+
+# the rigid motion G of `corner-turned` (a rotation about a generic axis, then a translation) and, per mesh, the
+# rotation Q^-1 it is authored under: instance k is G Q_k, a different transform for each
+TURN_G = (_rotation((1.0, 2.0, 3.0), 0.55), np.array([0.3, -0.2, 0.4]))
+TURN_Q = [_rotation((2.0, -1.0, 0.5), 0.4), _rotation((-1.0, 1.0, 2.0), -0.7), _rotation((0.5, 3.0, -1.0), 1.1)]
+
+
+def corner_turned_scene(variant):
+    """corner_scene("plain" / "stochastic") with the whole world -- instances, camera, lights -- under the rigid motion
+    TURN_G (the sky stays where it is: another scene, not the corner seen from elsewhere).  Mesh k is authored rotated
+    by Q_k^-1 (vertices and normals) and instanced with G Q_k, so every instance carries a different rotation, no
+    world normal is axis-aligned, and a hit at any depth needs its instance's normal matrix."""
+    sd = corner_scene(variant)
+    G, g = TURN_G
+    meshes, inst = [], []
+    for k, m in enumerate(sd.meshes):
+        Qi = TURN_Q[k].T
+        Pp = np.asarray(m.vertices, np.float64).reshape(2, 3, 3) @ Qi.T
+        Nn = np.asarray(m.fixed_normals, np.float64).reshape(-1, 4)[:, :3].reshape(2, 3, 3) @ Qi.T
+        tex = {key: getattr(m, key) for key in ("albedo", "metalness", "emission") if getattr(m, key) >= 0}
+        meshes.append(SQ._mesh(Pp, Nn, np.asarray(m.fixed_uvs, np.float64).reshape(2, 3, 2), **tex))
+        T = np.eye(4)
+        T[:3, :3], T[:3, 3] = G @ TURN_Q[k], g
+        inst.append((k, T.astype(F)))
+
+    def move(p):
+        return (np.asarray(p, np.float64) @ G.T + g).astype(F)
+
+    lg = sd.lights
+    lights = scenes.Lights(move(lg.point_pos), lg.point_col.copy(), move(lg.dir_pos), lg.dir_col.copy(),
+                           move(lg.spot_pos), lg.spot_col.copy(), (np.asarray(lg.spot_rot, np.float64) @ G.T).astype(F))
+    return scenes.SceneData(meshes, sd.textures, inst, lights, sd.sky, move(sd.cam_pos), move(sd.cam_target),
+                            "corner-turned-" + variant)
+
+
 def glass_over_floor_scene():
     tex = [np.array([[0x00C0B0A0]], np.uint32), np.array([[(128 << 8) | 128]], np.uint32),
            np.array([[0x00203040]], np.uint32)]
@@ -133,6 +179,8 @@ def scene_table():
     t["corner-plain"] = (corner_scene("plain"), ["floor", "wall", None], (2, 3, 4))
     t["corner-stochastic"] = (corner_scene("stochastic"), ["floor", "wall", None], (3,))
     t["corner-area"] = (corner_scene("area"), ["floor", "wall", None], (1, 3))
+    t["corner-turned-plain"] = (corner_turned_scene("plain"), ["floor", "wall", None], (3,))
+    t["corner-turned-stochastic"] = (corner_turned_scene("stochastic"), ["floor", "wall", None], (3,))
     t["glass-over-floor"] = (glass_over_floor_scene(), ["floor", "glass"], (3, 4))
     return t
 
@@ -140,13 +188,15 @@ def scene_table():
 STAT_CASES = [(name, b) for name, b in
               [(f"sky-floor-{r}-{m}", b) for r, m in Q.MATERIALS for b in (2, 3)]
               + [("corner-plain", 2), ("corner-plain", 3), ("corner-plain", 4), ("corner-stochastic", 3),
-                 ("corner-area", 1), ("corner-area", 3), ("glass-over-floor", 3), ("glass-over-floor", 4)]]
+                 ("corner-area", 1), ("corner-area", 3), ("glass-over-floor", 3), ("glass-over-floor", 4),
+                 ("corner-turned-plain", 3), ("corner-turned-stochastic", 3)]]
 
 
 def scene_flags(name):
-    """test_gpu_estimator's flags for the scene (FLAGS carries the stochastic bit), without it for corner-plain."""
+    """test_gpu_estimator's flags for the scene (FLAGS carries the stochastic bit), without it for corner-plain and
+    corner-turned-plain."""
     f = Q.scene_flags(scene_table()[name][0]) if name in scene_table() else Q.scene_flags(corner_scene("mirror"))
-    return f & ~_lib.FLAG_STOCHASTIC if name == "corner-plain" else f
+    return f & ~_lib.FLAG_STOCHASTIC if name in ("corner-plain", "corner-turned-plain") else f
 
 
 @functools.lru_cache(None)

@@ -24,6 +24,8 @@ What the reference is held to:
         spec_below_horizon_ends_path      sky-floor (1, 0), bounces 2
         last_segment_weighted_everywhere  corner-area, bounces 1
         glass_children_swapped            glass-over-floor, bounces 3
+        bounced_ray_not_transformed       corner-turned-plain, bounces 3 (a hit at depth >= 1 shaded with the
+                                          rectangle's object-space normal; moved / needed 7 to 9)
       Smallest margin: direct_not_scaled_by_throughput, 2.8 times what is needed in blue (0.8 in red): the lobe mixture
       hides most of it (the specular lobe's throughput 1 / p is above 1, the diffuse one's below), which is why the
       corner's floor is all metal.  The weighted last segment moves corner-area at bounces 3 by 0.05 of its bound -- the
@@ -38,13 +40,14 @@ seen on the oracle, as largest pixel / largest channel sum:
   corner-stochastic     bounces 3: 2.11 / 0.37
   corner-area           bounces 1: 2.23 / 0.39   bounces 3: 3.05 / 1.50
   glass-over-floor      bounces 3: 2.57 / 1.22   bounces 4: 2.51 / 1.21
+  corner-turned         plain, bounces 3: 2.80 / 2.17   stochastic, bounces 3: 2.47 / 0.55
   mirror-corner         largest error / tolerance 0.0019
 (the cases share their seeds: the same sign of the summed deviation in most of them is one draw, not fourteen).
 With a (0.25, 1) floor in the corner one pixel of corner-stochastic stood at z = 6.08: the narrow lobe's BRDF towards a
 point light is a heavy-tailed term, whose sigma 16384 paths underestimate by half (65536 paths of three other seeds
 and four other blocks of 4096 oracle frames agree with each other); the corner's floor is (0.5, 1) for that reason.
 
-The reference's CPU time: 3 to 7 s per case, 60 tested pixels x 16384 paths each (the 14 cases together about 60 s);
+The reference's CPU time: 3 to 7 s per case, 60 tested pixels x 16384 paths each (the 16 cases together about 70 s);
 the oracle's 4096 frames take 3 to 6 s per case, a slipped run of 8192 paths about 2 s.
 """
 import numpy as np
@@ -68,6 +71,7 @@ SLIP_CASES = {
     "spec_below_horizon_ends_path": ("sky-floor-1.0-0.0", 2),
     "last_segment_weighted_everywhere": ("corner-area", 1),
     "glass_children_swapped": ("glass-over-floor", 3),
+    "bounced_ray_not_transformed": ("corner-turned-plain", 3),
 }
 
 
